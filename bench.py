@@ -6,11 +6,18 @@ in HBM) against this GPU's 32 resident 8-MiB filters (m = 2^26), producing the
 (filters shard one subset per GPU, weak scaling) and the step also all-gathers
 the hit bitmaps over RCCL/xGMI. value = probes of all ranks / max-rank time.
 
-Also reported (same JSON line): C2 build keys/s (1M keys -> one 16 MiB filter),
-the dominant kernel's roofline (HIP events on its own stream), the CPU oracle
-baseline (rank 0, N = 1), and the PCIe-inclusive end-to-end probe rate.
+A plain run does only what that figure needs: it sets up, runs --warmup steps
+of the FilterSet probe (the library's read path), times --steps of them,
+writes the last step's hit map when --dump-outputs is given, and prints the
+line. With --full the per-filter (tiled) path is timed as well and the faster
+of the two is the headline, and the same JSON line also reports: C2 build
+keys/s (1M keys -> one 16 MiB filter), the dominant kernel's roofline (HIP
+events on its own stream), the CPU oracle baseline (rank 0, N = 1), the
+PCIe-inclusive end-to-end probe rate, cold-cache and rotating-batch steps,
+the zone gate, the read path, the wide fan-out, the flush producer, the
+per-key call and the C4 and C5 legs with their golden and oracle checks.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 
 `python bench.py --gpus N` (N > 1, no WORLD_SIZE in the environment) starts
@@ -50,6 +57,13 @@ def parse():
                         "(m=2^25) split over the GPUs")
     p.add_argument("--steps", type=int, default=200)
     p.add_argument("--warmup", type=int, default=10)
+    p.add_argument("--full", action="store_true",
+                   help="c3 / c5 line: also time the per-filter (tiled) path (the faster path is the headline) and run "
+                        "every secondary leg, roofline, CPU baseline and golden / oracle check of the line (minutes); "
+                        "without it the run times --steps steps of the FilterSet probe and prints the headline alone")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="c3 / c5 line: after the timed steps, write what the headline path's last timed step returned "
+                        "(the hit map, DIR/*.npy in float32 / float64: dump_outputs) for comparing two builds")
     p.add_argument("--leg-steps", type=int, default=200,
                    help="steps of each secondary leg (build, read path, zone, flush/4, rotating, one lane): "
                         "at least --steps; the headline leg times exactly --steps")
@@ -107,6 +121,8 @@ def parse():
     a = p.parse_args()
     if a.n_keys is None:
         a.n_keys = 10_000_000 if a.workload == "c5" else 1 << 20
+    if a.dump_outputs and (a.workload == "c4" or a.leg or a.dry_run):
+        p.error("--dump-outputs writes the probe line's hit map: not with --workload c4, --leg or --dry-run")
     return a
 
 
@@ -521,7 +537,10 @@ def main():
     LK = max(args.steps, args.leg_steps)
     probes_per_step = n * nf_total
     legs = {}
-    for name, fn in (("tiled", step_tiled), ("filterset", step_set)):
+    # a plain run times the FilterSet path alone; --full times the per-filter
+    # path too and takes the faster of the two as the headline
+    paths = (("tiled", step_tiled), ("filterset", step_set)) if args.full else (("filterset", step_set),)
+    for name, fn in paths:
         with guard("warmup"):
             for _ in range(args.warmup):
                 fn()
@@ -530,11 +549,123 @@ def main():
         legs[name] = {"el": el_leg, "value": probes_per_step / (el_leg / args.steps),
                       "ms_per_step": el_leg / args.steps * 1e3, "fn": fn,
                       "region_us_per_step": region["ms"] * 1e3 / region["k"]}
+        if args.dump_outputs and rank == 0:
+            # what the leg's last timed step returned (the next leg reuses the lanes' buffers)
+            legs[name]["last"] = hits_all_bufs[(step_no[0] - 1) % P].cpu().numpy()
     best = max(legs, key=lambda k: legs[k]["value"])
     el = legs[best]["el"]
     step = legs[best]["fn"]
     ms_step = el / args.steps * 1e3
     value = legs[best]["value"]
+    if "last" in legs[best]:
+        dump_outputs(args.dump_outputs, legs[best]["last"].view(np.uint64), n)
+
+    def check_hits():
+        # Every rank checks its own rows and, in the exchanged map, the rows
+        # of the next rank, so each rank's slice is verified as received by
+        # another rank; the verdicts are combined over all ranks.
+        from oracle import oracle
+
+        def oracle_rows(lo, hi):
+            refs = []
+            for f in range(lo, hi):
+                o = oracle.OracleFilter(m)
+                o.insert_fixed(workload.key_range(seed_base + f, kpf))
+                refs.append(o)
+            return oracle.probe_fixed(refs, look_np, threads=8)
+
+        step()  # the headline leg again (with --full the zone leg ran after it)
+        torch.cuda.synchronize(dev)
+        expect = oracle_rows(f_lo, f_lo + F)
+        got = hits_bufs[(step_no[0] - 1) % P].cpu().numpy().view(np.uint64)
+        good = bool(np.array_equal(got, expect))
+        if use_dist:
+            full = hits_all_bufs[(step_no[0] - 1) % P].cpu().numpy().view(np.uint64)
+            good &= bool(np.array_equal(full[f_lo:f_lo + F], expect))
+            if world > 1:
+                nlo, nhi = shard_range(nf_total, world, (rank + 1) % world)
+                good &= bool(np.array_equal(full[nlo:nhi], oracle_rows(nlo, nhi)))
+            flag = torch.tensor([1 if good else 0], dtype=torch.int32, device=red_dev)
+            with guard("check"):
+                dist.all_reduce(flag, op=dist.ReduceOp.MIN)
+            good = bool(flag.item())
+        assert good, "bench hits differ from the oracle"
+        if rank == 0:
+            log("[check] hits bit-exact vs oracle" +
+                (" (local rows on every rank, and every rank's rows in another rank's exchanged map)"
+                 if use_dist else ""))
+
+    def sparse_fit():
+        if not use_sparse:
+            return None
+        # every step's packs held all set bits: every exchanged map was complete
+        fit = bool(int(x_ok.item()))
+        if not fit:
+            log(f"[rank {rank}] ERROR: a sparse exchange overflowed cap={cap}; its map was incomplete, "
+                "so the timed steps did not all exchange the full map: the line is marked invalid")
+        return fit
+
+    def headline(x_fit):
+        """The line's own fields: the headline figure and the run's shape (a
+        plain run prints these alone; --full adds every leg's field)."""
+        # the BASELINE config name only when the shape is exactly that config's
+        c3_shape = (n == 1 << 20 and F == 32 and m == 1 << 26 and kpf == 1 << 19)
+        c5_shape = (n == 10_000_000 and F == 32 and m == 1 << 26 and kpf == 1 << 19 and seed_base == 1000)
+        wl_label = ("C3" if args.workload == "c3" and c3_shape else
+                    "C5 rank-slice" if args.workload == "c5" and c5_shape else "custom")
+        line = {
+            "metric": METRIC, "value": round(value, 1), "unit": "probes/s",
+            "n_gpus": xcomm.world if xcomm is not None else world,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_step, 4),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32",
+            "data": "synthetic (splitmix64 hex keys, SURVEY.md §8d)",
+            "config": {"workload": f"{wl_label} probe: {n} 16-B keys x {F} filters/GPU x {m // 8 // 2**20} MiB "
+                                   f"(m=2^{m.bit_length() - 1}), filters built from {kpf} keys each",
+                       "n_keys": n, "filters_per_gpu": F, "filters_total": nf_total, "m_bits": m,
+                       "keys_per_filter": kpf,
+                       "parallelism": "filter-sharded" + (
+                           (", RCCL all-gather of hit bitmaps" + (
+                               " as set-bit positions (sparse packs)" if use_sparse else
+                               " after each probe"))
+                           if use_dist else ""),
+                       "pipeline_lanes": P},
+            "exchange": (dict(xstats, mode="sparse", cap=cap, all_fit=x_fit) if use_sparse else
+                         {"mode": "dense"} if use_dist else None),
+            "path": best, "full": args.full,
+        }
+        if rccl_world is not None:
+            line["rccl_world"] = rccl_world
+        if x_fit is False:
+            line["valid"] = False
+        if rehearse:
+            line["rehearsal"] = (f"{world} ranks on ONE GPU over the host transport (gloo): checks the N-rank "
+                                 "flow, not a scaling measurement")
+            line["valid"] = False
+        return line
+
+    def finish(x_fit):
+        if use_dist:
+            with guard("teardown"):
+                torch.cuda.synchronize(dev)
+                dist.barrier()
+            if _WD is not None:
+                _WD.comm = None
+            xcomm.close()
+            dist.destroy_process_group()
+        if x_fit is False:
+            sys.exit(3)
+
+    if not args.full:
+        if args.check:
+            check_hits()
+        x_fit = sparse_fit()
+        if rank == 0:
+            line = headline(x_fit)
+            line.update({"region_us_per_step": round(legs[best]["region_us_per_step"], 2),
+                         "filterset": {"build_all_ms": round(set_build_ms, 3), "bytes": m * (4 if F <= 32 else 8)},
+                         "roofline": None, "cpu_baseline": None})
+            emit(line, result, args.full_line)
+        return finish(x_fit)
 
     # ---- separate profiled pass: per-kernel durations from HIP events on `sh`
     def kernel_ms(names, fn, k):
@@ -1005,77 +1136,17 @@ def main():
         c5 = run_c5()
 
     if args.check:
-        # Every rank checks its own rows and, in the exchanged map, the rows
-        # of the next rank, so each rank's slice is verified as received by
-        # another rank; the verdicts are combined over all ranks.
-        from oracle import oracle
-
-        def oracle_rows(lo, hi):
-            refs = []
-            for f in range(lo, hi):
-                o = oracle.OracleFilter(m)
-                o.insert_fixed(workload.key_range(seed_base + f, kpf))
-                refs.append(o)
-            return oracle.probe_fixed(refs, look_np, threads=8)
-
-        step()  # the headline leg again (the zone leg ran after it)
-        torch.cuda.synchronize(dev)
-        expect = oracle_rows(f_lo, f_lo + F)
-        got = hits_bufs[(step_no[0] - 1) % P].cpu().numpy().view(np.uint64)
-        good = bool(np.array_equal(got, expect))
-        if use_dist:
-            full = hits_all_bufs[(step_no[0] - 1) % P].cpu().numpy().view(np.uint64)
-            good &= bool(np.array_equal(full[f_lo:f_lo + F], expect))
-            if world > 1:
-                nlo, nhi = shard_range(nf_total, world, (rank + 1) % world)
-                good &= bool(np.array_equal(full[nlo:nhi], oracle_rows(nlo, nhi)))
-            flag = torch.tensor([1 if good else 0], dtype=torch.int32, device=red_dev)
-            with guard("check"):
-                dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-            good = bool(flag.item())
-        assert good, "bench hits differ from the oracle"
-        if rank == 0:
-            log("[check] hits bit-exact vs oracle" +
-                (" (local rows on every rank, and every rank's rows in another rank's exchanged map)"
-                 if use_dist else ""))
+        check_hits()
 
     cpu = None
     if rank == 0 and world == 1 and not args.no_cpu and args.workload == "c3":
         cpu = cpu_baseline(look_np, F, m, kpf, args.build_keys, args.build_m_bits)
         log(f"[cpu] {cpu}")
 
-    x_fit = None
-    if use_sparse:  # every step's packs held all set bits: every exchanged map was complete
-        x_fit = bool(int(x_ok.item()))
-        if not x_fit:
-            log(f"[rank {rank}] ERROR: a sparse exchange overflowed cap={cap}; its map was incomplete, "
-                "so the timed steps did not all exchange the full map: the line is marked invalid")
-
-    # the BASELINE config name only when the shape is exactly that config's
-    c3_shape = (n == 1 << 20 and F == 32 and m == 1 << 26 and kpf == 1 << 19)
-    c5_shape = (n == 10_000_000 and F == 32 and m == 1 << 26 and kpf == 1 << 19 and seed_base == 1000)
-    wl_label = ("C3" if args.workload == "c3" and c3_shape else
-                "C5 rank-slice" if args.workload == "c5" and c5_shape else "custom")
+    x_fit = sparse_fit()
     if rank == 0:
-        line = {
-            "metric": METRIC, "value": round(value, 1), "unit": "probes/s",
-            "n_gpus": xcomm.world if xcomm is not None else world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_step, 4),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32",
-            "data": "synthetic (splitmix64 hex keys, SURVEY.md §8d)",
-            "config": {"workload": f"{wl_label} probe: {n} 16-B keys x {F} filters/GPU x {m // 8 // 2**20} MiB "
-                                   f"(m=2^{m.bit_length() - 1}), filters built from {kpf} keys each",
-                       "n_keys": n, "filters_per_gpu": F, "filters_total": nf_total, "m_bits": m,
-                       "keys_per_filter": kpf,
-                       "parallelism": "filter-sharded" + (
-                           (", RCCL all-gather of hit bitmaps" + (
-                               " as set-bit positions (sparse packs)" if use_sparse else
-                               " after each probe"))
-                           if use_dist else ""),
-                       "pipeline_lanes": P},
-            "exchange": (dict(xstats, mode="sparse", cap=cap, all_fit=x_fit) if use_sparse else
-                         {"mode": "dense"} if use_dist else None),
-            "path": best,
+        line = headline(x_fit)
+        line.update({
             "kernels_us": {k: round(v["avg_us"], 2) for k, v in kprof.items()},
             "alt_paths": {k: {"value": round(v["value"], 1), "ms_per_step": round(v["ms_per_step"], 4)}
                           for k, v in legs.items() if k != best},
@@ -1085,26 +1156,9 @@ def main():
             "cold": cold, "rotating_batches": rot, "roofline": roof, "cpu_baseline": cpu, "build": build, "e2e": e2e,
             "zone_gate": zone, "read_path": read, "flush": flush, "may_contain": may_contain,
             "c4": c4, "c5": c5, "wide_fanout": wide,
-        }
-        if rccl_world is not None:
-            line["rccl_world"] = rccl_world
-        if x_fit is False:
-            line["valid"] = False
-        if rehearse:
-            line["rehearsal"] = (f"{world} ranks on ONE GPU over the host transport (gloo): checks the N-rank "
-                                 "flow, not a scaling measurement")
-            line["valid"] = False
+        })
         emit(line, result, args.full_line)
-    if use_dist:
-        with guard("teardown"):
-            torch.cuda.synchronize(dev)
-            dist.barrier()
-        if _WD is not None:
-            _WD.comm = None
-        xcomm.close()
-        dist.destroy_process_group()
-    if x_fit is False:
-        sys.exit(3)
+    finish(x_fit)
 
 
 # ---- the result line -------------------------------------------------------
@@ -1179,6 +1233,42 @@ def emit(line: dict, result, full_path=None) -> None:
         with open(full_path, "w") as fh:
             fh.write(json.dumps(line) + "\n")
     print(json.dumps(compact_line(line), separators=(",", ":")), file=result, flush=True)
+
+
+DUMP_WORD_BYTES = 24 << 20  # --dump-outputs: hit_words.npy at most this large
+DUMP_KEY_BYTES = 32 << 20   # ... and hit_sample.npy (64 MB in all with the 2 MB of sample indices)
+
+
+def dump_outputs(path: str, hits: np.ndarray, n: int) -> None:
+    """--dump-outputs DIR: the [filters][ceil(n / 64)] uint64 hit map that the
+    headline path's last timed step returned (bit i of row f = filter f may
+    contain lookup key i), written so that two builds compare file for file
+    (the inputs are the seeded workload, identical from run to run):
+
+    hit_words.npy        float32 [filters][4 x words]: every 64-bit word as
+                         its four 16-bit parts, low part first (exact in
+                         float32); the whole map at C3, and for a map over
+                         DUMP_WORD_BYTES a fixed seeded sample of its word
+                         columns (hit_word_columns.npy, float64, names them)
+    hit_sample.npy       float32 [filters][S]: the hit bit (0 / 1) of S
+                         lookup keys, a fixed seeded sample of the batch
+    hit_sample_keys.npy  float64 [S]: those keys' indices in the batch"""
+    os.makedirs(path, exist_ok=True)
+    hits = np.ascontiguousarray(hits, dtype="<u8")
+    rows, words = hits.shape
+    keep = DUMP_WORD_BYTES // (rows * 16)
+    if words > keep:
+        cols = np.sort(np.random.default_rng(64).choice(words, keep, replace=False))
+        np.save(os.path.join(path, "hit_word_columns.npy"), cols.astype(np.float64))
+        part = np.ascontiguousarray(hits[:, cols])
+    else:
+        part = hits
+    np.save(os.path.join(path, "hit_words.npy"), part.view("<u2").astype(np.float32))
+    s = min(n, DUMP_KEY_BYTES // (rows * 4))
+    idx = np.sort(np.random.default_rng(16).choice(n, s, replace=False)) if s < n else np.arange(n)
+    bits = (hits[:, idx >> 6] >> (idx & 63).astype(np.uint64)) & np.uint64(1)
+    np.save(os.path.join(path, "hit_sample.npy"), bits.astype(np.float32))
+    np.save(os.path.join(path, "hit_sample_keys.npy"), idx.astype(np.float64))
 
 
 def _golden():

@@ -41,6 +41,53 @@ def test_driver_flags_parse():
         _parse(["--build-streams", "5"])  # GPU_MAX_HW_QUEUES is 4 on the box
 
 
+def test_plain_run_is_the_headline_alone_and_full_is_an_option():
+    a = _parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (7, 2)
+    a = _parse(["--full", "--dump-outputs", "somewhere"])
+    assert a.full is True and a.dump_outputs == "somewhere"
+    for other in (["--workload", "c4"], ["--leg", "c2"], ["--dry-run"]):  # no hit map to write
+        with pytest.raises(SystemExit):
+            _parse(["--dump-outputs", "somewhere"] + other)
+
+
+@pytest.mark.parametrize("rows,n", [(3, 1000), (32, 1 << 16)])
+def test_dump_outputs_holds_the_hit_map(tmp_path, monkeypatch, rows, n):
+    """The dumped arrays are float32 / float64, give back the map they were
+    made from (every word from its four 16-bit parts, the sampled keys' bits),
+    and are the same files for the same map; a map over the word budget is
+    sampled by columns that the dump names."""
+    import numpy as np
+    words = (n + 63) // 64
+    hits = np.random.default_rng(5).integers(0, 1 << 63, (rows, words), dtype=np.uint64) * np.uint64(2) + np.uint64(1)
+    load = lambda d, f: np.load(os.path.join(d, f))
+    a, b = str(tmp_path / "a"), str(tmp_path / "b")
+    bench.dump_outputs(a, hits, n)
+    bench.dump_outputs(b, hits.copy(), n)
+    assert sorted(os.listdir(a)) == ["hit_sample.npy", "hit_sample_keys.npy", "hit_words.npy"]
+    for f in os.listdir(a):
+        assert load(a, f).dtype in (np.float32, np.float64) and np.array_equal(load(a, f), load(b, f))
+    w = load(a, "hit_words.npy").astype(np.uint64).reshape(rows, words, 4)
+    assert np.array_equal(w[..., 0] | w[..., 1] << 16 | w[..., 2] << 32 | w[..., 3] << 48, hits)
+    idx = load(a, "hit_sample_keys.npy").astype(np.int64)
+    assert len(idx) == n and np.array_equal(idx, np.arange(n))
+    assert np.array_equal(load(a, "hit_sample.npy"), ((hits[:, idx >> 6] >> (idx & 63).astype(np.uint64)) & 1))
+    # over the budgets: seeded column and key samples, the same from run to run
+    monkeypatch.setattr(bench, "DUMP_WORD_BYTES", rows * 16 * 5)
+    monkeypatch.setattr(bench, "DUMP_KEY_BYTES", rows * 4 * 100)
+    c, d = str(tmp_path / "c"), str(tmp_path / "d")
+    bench.dump_outputs(c, hits, n)
+    bench.dump_outputs(d, hits, n)
+    cols = load(c, "hit_word_columns.npy").astype(np.int64)
+    assert len(cols) == 5 and len(set(cols)) == 5 and np.array_equal(cols, load(d, "hit_word_columns.npy"))
+    w = load(c, "hit_words.npy").astype(np.uint64).reshape(rows, 5, 4)
+    assert np.array_equal(w[..., 0] | w[..., 1] << 16 | w[..., 2] << 32 | w[..., 3] << 48, hits[:, cols])
+    idx = load(c, "hit_sample_keys.npy").astype(np.int64)
+    assert len(idx) == 100 and len(set(idx)) == 100 and np.array_equal(idx, load(d, "hit_sample_keys.npy"))
+    assert np.array_equal(load(c, "hit_sample.npy"), ((hits[:, idx >> 6] >> (idx & 63).astype(np.uint64)) & 1))
+    assert sum(os.path.getsize(os.path.join(c, f)) for f in os.listdir(c)) < 64e6
+
+
 def test_metric_names_the_baseline_metric():
     import json
     with open(os.path.join(ROOT, "BASELINE.json")) as fh:

@@ -20,7 +20,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SMALL = ["--steps", "4", "--warmup", "2", "--filters", "5", "--m-bits", str(1 << 22), "--keys-per-filter",
+SMALL = ["--full", "--steps", "4", "--warmup", "2", "--filters", "5", "--m-bits", str(1 << 22), "--keys-per-filter",
          str(1 << 15), "--n-keys", "100000", "--build-keys", str(1 << 16), "--build-m-bits", str(1 << 20),
          "--no-cpu", "--no-e2e", "--no-cold", "--no-read", "--no-flush", "--no-c4", "--no-c5", "--check"]
 
@@ -70,7 +70,7 @@ def test_bench_rehearsal_c5(gpu, world, sparse):
     """--workload c5 at world > 1 in a small shape (C5's filters and seeds,
     200K lookups): each rank's 32-filter slice and the exchanged map against
     the oracle."""
-    d, err = _run(world, ["--workload", "c5", "--n-keys", "200000", "--steps", "4", "--warmup", "1",
+    d, err = _run(world, ["--full", "--workload", "c5", "--n-keys", "200000", "--steps", "4", "--warmup", "1",
                           "--no-cpu", "--no-e2e", "--no-cold", "--no-read", "--no-flush", "--no-zone", "--check"],
                   sparse)
     assert d["config"]["filters_total"] == 32 * world and d["config"]["m_bits"] == 1 << 26

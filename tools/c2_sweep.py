@@ -14,7 +14,7 @@ if len(sys.argv) > 1:
     SETTINGS = json.loads(sys.argv[1])
 for env in SETTINGS:
     e = dict(os.environ, **env)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "expbench.py"), "--steps", "20", "--warmup", "5",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "expbench.py"), "--full", "--steps", "20", "--warmup", "5",
                         "--leg-steps", "200", "--no-cpu", "--no-e2e", "--no-cold", "--no-zone", "--no-read",
                         "--no-flush", "--no-c4", "--no-c5", "--no-wide"],
                        capture_output=True, text=True, timeout=300, env=e, cwd=ROOT)

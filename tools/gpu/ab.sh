@@ -34,7 +34,7 @@ for rep in $(seq 1 $REPS); do
     out=$O/${label}_$rep
     case $LEG in
       c2_lane) cmd=(./build/tools/c2_lane "${lib:-lsmt_amd}/libcassbloom.so") ;;
-      c3) cmd=(bench.py --no-cpu --steps $STEPS --warmup $WARMUP $ARGS) ;;
+      c3) cmd=(bench.py --full --no-cpu --steps $STEPS --warmup $WARMUP $ARGS) ;;
       c4) cmd=(bench.py --workload c4 --no-cpu --steps $STEPS --warmup $WARMUP $ARGS) ;;
       *) cmd=(bench.py --leg $LEG --no-cpu --steps $STEPS --warmup $WARMUP $ARGS) ;;
     esac

@@ -22,7 +22,7 @@ mkdir -p $OUT
 LANE1="--probe-streams 1"
 case $SHAPE in
   c2) BENCH="python bench.py --leg c2 --no-cpu --no-cold --steps 50 --warmup 5"; META="shape=c2"; LANE1="--build-streams 1" ;;
-  c3) BENCH="python bench.py --no-cpu --no-e2e --no-cold --no-c4 --no-c5 --no-wide --steps 50 --warmup 1000"; META="shape=c3" ;;
+  c3) BENCH="python bench.py --full --no-cpu --no-e2e --no-cold --no-c4 --no-c5 --no-wide --steps 50 --warmup 1000"; META="shape=c3" ;;
   c4) BENCH="python bench.py --workload c4 --no-cpu --steps 50 --warmup 5"; META="shape=c4 filters_per_launch=64" ;;
   c5) BENCH="python bench.py --leg c5 --no-cpu --steps 20 --warmup 3"; META="shape=c5" ;;
   wide) BENCH="python bench.py --leg wide --no-cpu --steps 10 --warmup 2"; META="shape=wide" ;;
