@@ -81,19 +81,13 @@ BlockPool g_pool;
 // blocks again (the A/B); CB_POOL_CONTIG=1 allocates slabs and large blocks
 // physically contiguous (hipDeviceMallocContiguous).
 bool small_blocks_on() {
-#ifdef CB_EXPERIMENTS
-  static const bool off = getenv("CB_POOL_SLAB") && getenv("CB_POOL_SLAB")[0] == '0';
-  return !off;
-#else
-  return true;
-#endif
+  static const bool on = cb::knob_int("CB_POOL_SLAB", 1) != 0;
+  return on;
 }
 
 hipError_t device_malloc(void** p, size_t bytes) {
-#ifdef CB_EXPERIMENTS
-  static const bool contig = getenv("CB_POOL_CONTIG") && getenv("CB_POOL_CONTIG")[0] == '1';
+  static const bool contig = cb::knob_int("CB_POOL_CONTIG", 0) == 1;
   if (contig) return hipExtMallocWithFlags(p, bytes, hipDeviceMallocContiguous);
-#endif
   return hipMalloc(p, bytes);
 }
 
@@ -787,7 +781,7 @@ int set_probe_zero_copy(const cb_filterset* set, const uint8_t* keys, uint32_t k
     HIP_TRY(cb::launch_wide_probe(keyk, set->mode, set->R, (const uint64_t*)set->words, set->used, ks, n, set->mp,
                                   zv ? &wz : nullptr, (uint64_t*)dh, (n + 63) / 64, s));
   } else {
-    HIP_TRY(cb::launch_set_probe(keyk, set->mode, set->width, set->words, set->any, set->used, ks, n,
+    HIP_TRY(cb::launch_set_probe(keyk, set->mode, set->width, set->words, set->used, ks, n,
                                  set->mp, zv, (uint64_t*)dh, (n + 63) / 64, s));
   }
   HIP_TRY(hipStreamSynchronize(s));  // the table is no longer read: no reader event needed
@@ -848,7 +842,7 @@ int set_probe_impl(const cb_filterset* set, const uint8_t* keys, const uint64_t*
   } else if (dense) {
     if ((rc = dense_probe(ws, set, sk.keyk, sk.ks, n, dhits, hwords, s))) return rc;
   } else {
-    HIP_TRY(cb::launch_set_probe(sk.keyk, set->mode, set->width, set->words, set->any, set->used,
+    HIP_TRY(cb::launch_set_probe(sk.keyk, set->mode, set->width, set->words, set->used,
                                  sk.ks, n, set->mp, (gated && set->zany) ? &zv : nullptr, dhits,
                                  hwords, s));
   }
@@ -910,7 +904,7 @@ int set_probe_device(const cb_filterset* set, const uint8_t* keys, uint32_t key_
     e = cb::launch_wide_probe(keyk, set->mode, set->R, (const uint64_t*)set->words, set->used, ks, n, set->mp,
                               (gated && set->zany) ? &wz : nullptr, hits, hwords, s);
   } else {
-    e = cb::launch_set_probe(keyk, set->mode, set->width, set->words, set->any, set->used, ks, n, set->mp,
+    e = cb::launch_set_probe(keyk, set->mode, set->width, set->words, set->used, ks, n, set->mp,
                              (gated && set->zany) ? &zv : nullptr, hits, hwords, s, sink_pack ? &sink : nullptr);
   }
   if (e != hipSuccess) {
@@ -1933,18 +1927,6 @@ int cb_set_create(uint64_t m_bits, uint32_t width, int device, cb_filterset** ou
     return fail(CB_ENOMEM, "device allocation failed for filter set words");
   }
   HIP_TRY(hipMemsetAsync(set->words, 0, bytes, nullptr));
-  if (width > 64) {  // wide sets keep no union words (the pre-test is a 32/64-slot experiment)
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    *out = set.release();
-    return CB_OK;
-  }
-  const size_t any_bytes = (size_t)((m_bits + 31) / 32) * 4;
-  if (pool_alloc(device, any_bytes, (void**)&set->any, &set->any_cap) != hipSuccess) {
-    set->any = nullptr;
-    pool_release(device, set->words, set->words_cap);
-    return fail(CB_ENOMEM, "device allocation failed for filter set union words");
-  }
-  HIP_TRY(hipMemsetAsync(set->any, 0, any_bytes, nullptr));
   HIP_TRY(hipStreamSynchronize(nullptr));
   *out = set.release();
   return CB_OK;
@@ -1955,7 +1937,6 @@ int cb_set_destroy(cb_filterset* set) {
   {
     DeviceGuard dg(set->device);
     pool_release(set->device, set->words, set->words_cap);  // (stream-ordered: no device sync)
-    pool_release(set->device, set->any, set->any_cap);
     if (set->zdev) (void)hipFree(set->zdev);
     if (set->wfw) (void)hipFree(set->wfw);
     for (void* z : set->zretired) (void)hipFree(z);
@@ -1988,9 +1969,9 @@ int cb_set_assign(cb_filterset* set, uint32_t slot, const cb_filter* f, void* st
     else
       HIP_TRY(cb::launch_wide_or_slot(f->words, set->m, slot, set->R, w, s));
   } else if (slot_dirty(set, slot)) {
-    HIP_TRY(cb::launch_set_put_slot(f->words, set->m, slot, set->width, set->words, set->any, s));
+    HIP_TRY(cb::launch_set_put_slot(f->words, set->m, slot, set->width, set->words, s));
   } else {
-    HIP_TRY(cb::launch_set_or_slot(f->words, set->m, slot, set->width, set->words, set->any, s));
+    HIP_TRY(cb::launch_set_or_slot(f->words, set->m, slot, set->width, set->words, s));
   }
   set->dirty[slot >> 6] |= 1ull << (slot & 63);
   set->used = std::max(set->used, slot + 1);
@@ -2032,7 +2013,7 @@ int cb_set_assign_all(cb_filterset* set, const cb_filter* const* filters, uint32
     HIP_TRY(cb::launch_wide_build((const uint32_t* const*)set->wfw, nf, set->m, set->R, (uint64_t*)set->words, s));
     HIP_TRY(hipStreamSynchronize(s));  // the pageable pointer array is copied, and wfw is reused
   } else {
-    HIP_TRY(cb::launch_set_build(fp, nf, set->m, set->width, set->words, set->any, s));
+    HIP_TRY(cb::launch_set_build(fp, nf, set->m, set->width, set->words, s));
   }
   set->used = nf;
   for (size_t j = 0; j < set->dirty.size(); ++j) {
@@ -2054,7 +2035,7 @@ int cb_set_clear_slot(cb_filterset* set, uint32_t slot, void* stream) {
   if (set_is_wide(set))
     HIP_TRY(cb::launch_wide_put_slot(nullptr, set->m, slot, set->R, (uint64_t*)set->words, (hipStream_t)stream));
   else
-    HIP_TRY(cb::launch_set_put_slot(nullptr, set->m, slot, set->width, set->words, set->any,
+    HIP_TRY(cb::launch_set_put_slot(nullptr, set->m, slot, set->width, set->words,
                                     (hipStream_t)stream));
   set->dirty[slot >> 6] &= ~(1ull << (slot & 63));
   return CB_OK;
@@ -2221,16 +2202,9 @@ int cb_filter_insert_fixed_many(cb_filter* const* filters, uint32_t nf, const ui
       }
     staged = true;
   }
-#ifdef CB_EXPERIMENTS
-  static const uint32_t batch_env = [] {  // filters per launch pair (tuning)
-    const char* v = getenv("CB_BUILD_BATCH");
-    const int b = v && *v ? atoi(v) : 0;
-    return b >= 1 && b <= (int)cb::kMaxBuildBatch ? (uint32_t)b : cb::kMaxBuildBatch;
-  }();
-  const uint32_t kBatch = batch_env;
-#else
-  const uint32_t kBatch = cb::kMaxBuildBatch;
-#endif
+  static const int batch_knob = cb::knob_int("CB_BUILD_BATCH", 0);  // filters per launch pair (tuning)
+  const uint32_t kBatch =
+      batch_knob >= 1 && batch_knob <= (int)cb::kMaxBuildBatch ? (uint32_t)batch_knob : cb::kMaxBuildBatch;
   const TilePlan p = cb::plan_build(f0->m, nmax, std::min<uint32_t>(nf, kBatch));
   for (uint32_t i = 0; i < nf; ++i)
     if (!covers(filters[i], p)) return fail(CB_EINVAL, "internal: build tile plan exceeds the filter allocation");

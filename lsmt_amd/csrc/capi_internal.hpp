@@ -21,6 +21,7 @@
 #include "filterset.hpp"
 #include "flush.hpp"
 #include "kernels.hpp"
+#include "knobs.hpp"
 #include "sstable.hpp"
 #include "wideset.hpp"
 #include "zone.hpp"
@@ -91,8 +92,7 @@ struct cb_filterset {
   int device = 0;
   uint32_t width = 32;
   void* words = nullptr;  // device, m (rounded up to 32) words of width bits
-  uint32_t* any = nullptr;  // device, ceil(m/32) words: bit p = (words[p] != 0)
-  size_t words_cap = 0, any_cap = 0;  // their pool blocks
+  size_t words_cap = 0;   // its pool block
   uint32_t used = 0;      // 1 + highest assigned slot
   std::vector<uint64_t> dirty;  // word j bit i: slot 64 j + i may hold set bits
   int mode = 0;

@@ -59,12 +59,8 @@ int table_search_impl(const cb_table* t, const uint8_t* keys, const uint64_t* of
 }
 
 bool buckets_enabled() {
-#ifdef CB_EXPERIMENTS
-  static const bool off = getenv("CB_NO_BUCKETS") && getenv("CB_NO_BUCKETS")[0] == '1';
+  static const bool off = cb::knob_int("CB_NO_BUCKETS", 0) == 1;
   return !off;
-#else
-  return true;
-#endif
 }
 
 // The key buckets (sstable.hpp) for a read on stream s: the first read of a
@@ -130,12 +126,10 @@ int wide_screen(Workspace& ws, const cb_table* const* tables, const std::vector<
                 hipStream_t s, cb::WideScreen* out) {
   const uint32_t nt = (uint32_t)views.size();
   uint32_t hbits = kScreenHbits;
-#ifdef CB_EXPERIMENTS
-  static const bool off = getenv("CB_NO_SCREEN") && getenv("CB_NO_SCREEN")[0] == '1';  // the A/B
+  static const bool off = cb::knob_int("CB_NO_SCREEN", 0) == 1;  // the A/B
   if (off) return CB_OK;
-  static const int env_h = getenv("CB_SCREEN_HBITS") ? atoi(getenv("CB_SCREEN_HBITS")) : -1;
-  if (env_h >= 0 && env_h <= 8) hbits = (uint32_t)env_h;
-#endif
+  static const int knob_h = cb::knob_int("CB_SCREEN_HBITS", -1);
+  if (knob_h >= 0 && knob_h <= 8) hbits = (uint32_t)knob_h;
   uint32_t bits = 0;
   for (const auto& v : views)
     if (v.bkt && v.fast()) {
@@ -315,11 +309,9 @@ int get_many_impl(const cb_table* const* tables, uint32_t nt, const uint64_t* hi
       ws.t_maps_sig.swap(msig);
     }
     const cb::DirMap* dmaps = (const cb::DirMap*)ws.t_maps.p;
-#ifdef CB_EXPERIMENTS
     // the A/B: maps found through the views (the round-5 staging)
-    static const bool no_maps = getenv("CB_WIDE_MAPS") && getenv("CB_WIDE_MAPS")[0] == '0';
+    static const bool no_maps = cb::knob_int("CB_WIDE_MAPS", 1) == 0;
     if (no_maps) dmaps = nullptr;
-#endif
     HIP_TRY(cb::launch_wide_get_many(sk.keyk, set->mode, set->R, (const uint64_t*)set->words, set->mp,
                                      set->zany ? &wz : nullptr, dviews, nt, (const cb::WideGroup*)ws.t_groups.p,
                                      need_slots ? drows : nullptr, sk.ks, n, dwhich, (uint64_t*)ws.t_line.p,
@@ -338,10 +330,8 @@ int get_many_impl(const cb_table* const* tables, uint32_t nt, const uint64_t* hi
   // batches of up to 256K keys: the decode scans the tile sums itself (one
   // launch fewer per batch); larger ones: the one-block scan between
   bool raw = n && n <= cb::decode_raw_max();  // (n = 0: the scan kernel writes voff[0] = 0)
-#ifdef CB_EXPERIMENTS
-  static const bool no_raw = getenv("CB_DECODE_RAW") && getenv("CB_DECODE_RAW")[0] == '0';
+  static const bool no_raw = cb::knob_int("CB_DECODE_RAW", 1) == 0;
   if (no_raw) raw = false;
-#endif
   if (!raw) HIP_TRY(cb::launch_tile_scan(tsum, cb::get_tiles(n), dvoff + n, s));
   if (!ws.htot) HIP_TRY(hipHostMalloc((void**)&ws.htot, kHostScratch, hipHostMallocDefault));
   if (async) {
@@ -513,13 +503,8 @@ namespace {
 // Bin-sort group target: ~n / 1536 records (six 1024-record group sorts per
 // CU on 256 CUs, one wave), at least 640, at most 1536 (2048-record sorts).
 uint32_t bin_group_target(uint64_t n) {
-#ifdef CB_EXPERIMENTS
-  static const int env = [] {
-    const char* v = getenv("CB_BIN_T");  // group size target (tuning); 0 disables the bin sort
-    return v && *v ? atoi(v) : -1;
-  }();
-  if (env >= 0) return (uint32_t)env;
-#endif
+  static const int knob = cb::knob_int("CB_BIN_T", -1);  // group size target (tuning); 0 disables the bin sort
+  if (knob >= 0) return (uint32_t)knob;
   return (uint32_t)std::min<uint64_t>(1536, std::max<uint64_t>(640, (n + 1535) / 1536));
 }
 

@@ -255,10 +255,8 @@ int new_comm(int rank, int world, int device, std::unique_ptr<cb_comm>* out) {
   // is enough, so no system-scope fence (an L2 write-back per record, paid
   // in GPU time every step; round 3 measured the zone-read events' fence)
   unsigned order_flags = hipEventDisableTiming | hipEventDisableSystemFence;
-#ifdef CB_EXPERIMENTS
-  if (const char* e = getenv("CB_ORDER_FENCE"); e && e[0] == '1')  // A/B: the fenced event
-    order_flags = hipEventDisableTiming;
-#endif
+  static const bool fenced = cb::knob_int("CB_ORDER_FENCE", 0) == 1;  // A/B: the fenced event
+  if (fenced) order_flags = hipEventDisableTiming;
   HIP_TRY(hipEventCreateWithFlags(&c->order, order_flags));
   *out = std::move(c);
   return CB_OK;

@@ -35,11 +35,11 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdlib>
 #include <type_traits>
 
 #include "blockscan.hpp"
 #include "filterset.hpp"
+#include "knobs.hpp"
 #include "profile.hpp"
 #include "setmask.hpp"
 
@@ -53,16 +53,8 @@ constexpr uint32_t kDenseNT = 1024;
 // of 7 keys per thread (C = 7168, 1396 blocks at C5) measured 209-211 us per
 // C5 step on three lanes; two of 5 (977 blocks) 194-196; three of 4 (814
 // blocks) 190-191 (experiment r05_c5nb, HISTORY.md, same box, alternating).
-#if defined(CB_EXPERIMENTS) && defined(CB_DENSE_KPT)
-constexpr uint32_t kDenseKPT = CB_DENSE_KPT;  // (experiment builds: keys per partition thread and batch)
-#else
-constexpr uint32_t kDenseKPT = 4;
-#endif
-#if defined(CB_EXPERIMENTS) && defined(CB_DENSE_NB)
-constexpr uint32_t kDenseNB = CB_DENSE_NB;  // (experiment builds: key batches per partition block)
-#else
-constexpr uint32_t kDenseNB = 3;
-#endif
+constexpr uint32_t kDenseKPT = CB_DENSE_KPT;  // keys per partition thread and batch
+constexpr uint32_t kDenseNB = CB_DENSE_NB;    // key batches per partition block
 constexpr uint32_t kDenseC = kDenseNT * kDenseKPT * kDenseNB;  // keys per partition block (a multiple of 64)
 static_assert(kDenseC % 64 == 0 && kDenseC < 65536, "block keys: whole hit words, u16 run starts");
 constexpr uint32_t kRegionBytes = 65536;  // one region of the set, staged in LDS
@@ -78,13 +70,7 @@ constexpr uint32_t kProbeU = 4;              // entries per lane per round of th
 // on three lanes went 209-211 -> 221-225 us (one lane 249 -> 242); at 4 keys
 // per thread (no spill) the batch needs two chunks and the set is streamed
 // twice: 265-268 us (experiment r05_c5part, HISTORY.md).
-#if defined(CB_EXPERIMENTS) && defined(CB_DENSE_PART_LB8)
-#define CB_DENSE_PART_WAVES 8
-#elif defined(CB_EXPERIMENTS) && defined(CB_DENSE_PART_W)
-#define CB_DENSE_PART_WAVES CB_DENSE_PART_W
-#else
-#define CB_DENSE_PART_WAVES 1
-#endif
+constexpr int kDensePartWaves = CB_DENSE_PART_W;
 
 // Dynamic LDS of a partition block over R regions: the R + 1 counts (padded)
 // and a discard word, then the block's C staged entries.
@@ -99,16 +85,8 @@ constexpr size_t dense_part_lds_max() { return dense_part_lds(kDenseMaxRegions);
 // as plain, and the entries alone non-temporal 143.4 us (round 6, HISTORY.md).
 // Experiment builds: CB_DENSE_ST 0 plain, 1 write-through, 2 non-temporal;
 // CB_DENSE_HST 0 the hit words plain.
-#if defined(CB_EXPERIMENTS) && defined(CB_DENSE_ST)
 constexpr int kDenseSt = CB_DENSE_ST;
-#else
-constexpr int kDenseSt = 2;
-#endif
-#if defined(CB_EXPERIMENTS) && defined(CB_DENSE_HST)
 constexpr bool kDenseHitsNt = CB_DENSE_HST;
-#else
-constexpr bool kDenseHitsNt = true;
-#endif
 typedef uint32_t dense_u32x4 __attribute__((ext_vector_type(4)));
 typedef int dense_i32x4 __attribute__((ext_vector_type(4)));
 
@@ -122,7 +100,7 @@ __device__ __forceinline__ uint32_t xcd_region(uint32_t bid, uint32_t R) {
 // Keys [k0 + blockIdx.x C, ...) of the chunk: positions, region bins, the
 // block's region-sorted entries and its column of the run-start table.
 template <int KEYK, int MODE, int W>
-__global__ __launch_bounds__(kDenseNT, CB_DENSE_PART_WAVES) void k_dense_part(KeySrc ks, uint64_t k0, uint64_t n, ModP mp,
+__global__ __launch_bounds__(kDenseNT, kDensePartWaves) void k_dense_part(KeySrc ks, uint64_t k0, uint64_t n, ModP mp,
                                                          uint32_t rshift, uint32_t R,
                                                          uint16_t* __restrict__ seg, uint32_t segstride,
                                                          uint2* __restrict__ ent, uint64_t* __restrict__ hits,
@@ -293,13 +271,17 @@ __device__ __forceinline__ uint32_t run_of(const uint32_t* P, uint32_t nblk, uin
   return lo - 1;
 }
 
-template <int W>
+// X: timing-only variant bits (CB_DENSE_X, experiment builds; the hits are
+// wrong): bit 0 skips the set[b] gathers, bit 1 the hit atomics. The product
+// instantiates X = 0 only.
+constexpr int kDenseX = CB_DENSE_X;
+template <int W, int X>
 __global__ __launch_bounds__(kDenseNT, 8) void k_dense_probe(const void* __restrict__ setp, uint64_t m,
                                                              uint32_t rshift, uint32_t R,
                                                              const uint16_t* __restrict__ seg, uint32_t segstride,
                                                              uint32_t nblk, const uint2* __restrict__ ent,
                                                              uint64_t k0, uint64_t* __restrict__ hits,
-                                                             uint64_t hwords, uint32_t used, uint32_t xflags) {
+                                                             uint64_t hwords, uint32_t used) {
   typedef typename std::conditional<W == 32, uint32_t, uint64_t>::type word_t;
   constexpr uint32_t NT = kDenseNT, C = kDenseC, P = kRegionBytes / sizeof(word_t);
   __shared__ __attribute__((aligned(16))) word_t stage[P];
@@ -372,11 +354,11 @@ __global__ __launch_bounds__(kDenseNT, 8) void k_dense_probe(const void* __restr
     for (uint32_t u = 0; u < kProbeU; ++u) va[u] = e[u].y != 0xFFFFFFFFu ? stage[e[u].y >> 16] : (word_t)0;
 #pragma unroll
     for (uint32_t u = 0; u < kProbeU; ++u)
-      vb[u] = va[u] ? ((xflags & 1u) ? va[u] : set[e[u].x]) : (word_t)0;  // src/bloom.rs:50's &&
+      vb[u] = va[u] ? ((X & 1) ? va[u] : set[e[u].x]) : (word_t)0;  // src/bloom.rs:50's &&
 #pragma unroll
     for (uint32_t u = 0; u < kProbeU; ++u) {
       word_t mask = va[u] & vb[u] & usedm;
-      if (mask && !(xflags & 2u)) {
+      if (mask && !(X & 2)) {
         const uint64_t key = k0 + (uint64_t)blk[u] * C + (e[u].y & 0xFFFFu);
         const unsigned long long bit = 1ull << (key & 63u);
         unsigned long long* row = reinterpret_cast<unsigned long long*>(hits) + key / 64;
@@ -470,13 +452,6 @@ hipError_t launch_set_probe_dense(int keyk, int mode, uint32_t width, const void
   uint16_t* seg = reinterpret_cast<uint16_t*>(reinterpret_cast<uint8_t*>(scratch) + (uint64_t)nblk0 * kDenseC * 8);
   uint16_t* segT = seg + (uint64_t)nblk0 * stride;
   const size_t lds1 = dense_part_lds(R);
-  uint32_t xflags = 0;
-#ifdef CB_EXPERIMENTS
-  // timing-only A/B (the hits are wrong): CB_DENSE_X bit 0 skips the set[b]
-  // gathers, bit 1 the hit atomics
-  static const uint32_t env_x = getenv("CB_DENSE_X") ? (uint32_t)atoi(getenv("CB_DENSE_X")) : 0u;
-  xflags = env_x;
-#endif
   for (uint64_t k0 = 0; k0 < n; k0 += chunk) {
     const uint64_t nk = n - k0 < chunk ? n - k0 : chunk;
     const uint32_t nblk = (uint32_t)((nk + kDenseC - 1) / kDenseC);
@@ -499,11 +474,11 @@ hipError_t launch_set_probe_dense(int keyk, int mode, uint32_t width, const void
     {
       ProfScope ps("k_dense_probe", s);
       if (width == 32)
-        hipLaunchKernelGGL((k_dense_probe<32>), dim3(R), dim3(kDenseNT), 0, s, set, mp.m, rshift, R, segT, tstride,
-                           nblk, ent, k0, hits, hwords, used, xflags);
+        hipLaunchKernelGGL((k_dense_probe<32, kDenseX>), dim3(R), dim3(kDenseNT), 0, s, set, mp.m, rshift, R, segT,
+                           tstride, nblk, ent, k0, hits, hwords, used);
       else
-        hipLaunchKernelGGL((k_dense_probe<64>), dim3(R), dim3(kDenseNT), 0, s, set, mp.m, rshift, R, segT, tstride,
-                           nblk, ent, k0, hits, hwords, used, xflags);
+        hipLaunchKernelGGL((k_dense_probe<64, kDenseX>), dim3(R), dim3(kDenseNT), 0, s, set, mp.m, rshift, R, segT,
+                           tstride, nblk, ent, k0, hits, hwords, used);
       hipError_t e = hipGetLastError();
       if (e != hipSuccess) return e;
     }

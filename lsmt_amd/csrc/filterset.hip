@@ -14,7 +14,6 @@
 // 64 B x distinct sectors touched by the a/b reads + 16 B/key + the hit bitmap.
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
 #include <type_traits>
 
 #include "blockscan.hpp"
@@ -25,8 +24,6 @@
 
 namespace cb {
 namespace {
-
-typedef const __attribute__((address_space(1))) uint64_t* gsp64;
 
 // In-register 32x32 bit transpose: on entry a[i] bit j = element (i, j); on
 // exit a[j] bit i = element (i, j). Every index is static after unrolling.
@@ -60,16 +57,12 @@ __device__ __forceinline__ void transpose32(uint32_t (&a)[32]) {
 // across threads), transposes, writes the 32 set words of the group.
 template <int W>
 __global__ __launch_bounds__(256) void k_set_build(FilterPtrs fp, uint32_t nf, uint64_t ngroups,
-                                                   uint64_t m, void* __restrict__ set,
-                                                   uint32_t* __restrict__ any) {
+                                                   uint64_t m, void* __restrict__ set) {
   const uint64_t stride = (uint64_t)gridDim.x * 256;
   for (uint64_t g = (uint64_t)blockIdx.x * 256 + threadIdx.x; g < ngroups; g += stride) {
-    uint32_t a[32], u = 0;
+    uint32_t a[32];
 #pragma unroll
-    for (int i = 0; i < 32; ++i) {
-      a[i] = (uint32_t)i < nf ? fp.w[i][g] : 0u;
-      u |= a[i];
-    }
+    for (int i = 0; i < 32; ++i) a[i] = (uint32_t)i < nf ? fp.w[i][g] : 0u;
     transpose32(a);
     const uint64_t p0 = g * 32;
     const uint32_t valid = (uint32_t)min<uint64_t>(32, m - p0);
@@ -87,10 +80,7 @@ __global__ __launch_bounds__(256) void k_set_build(FilterPtrs fp, uint32_t nf, u
     } else {
       uint32_t c[32];
 #pragma unroll
-      for (int i = 0; i < 32; ++i) {
-        c[i] = (uint32_t)(32 + i) < nf ? fp.w[32 + i][g] : 0u;
-        u |= c[i];
-      }
+      for (int i = 0; i < 32; ++i) c[i] = (uint32_t)(32 + i) < nf ? fp.w[32 + i][g] : 0u;
       transpose32(c);
       uint32_t* out = reinterpret_cast<uint32_t*>(set) + 2 * p0;  // (lo, hi) per position
       if (valid == 32) {
@@ -106,7 +96,6 @@ __global__ __launch_bounds__(256) void k_set_build(FilterPtrs fp, uint32_t nf, u
           }
       }
     }
-    any[g] = u;
   }
 }
 
@@ -116,12 +105,10 @@ __global__ __launch_bounds__(256) void k_set_build(FilterPtrs fp, uint32_t nf, u
 template <int W>
 __global__ __launch_bounds__(256) void k_set_or_slot(const uint32_t* __restrict__ words,
                                                      uint64_t nwords, uint32_t slot,
-                                                     void* __restrict__ set,
-                                                     uint32_t* __restrict__ any) {
+                                                     void* __restrict__ set) {
   const uint64_t stride = (uint64_t)gridDim.x * 256;
   for (uint64_t w = (uint64_t)blockIdx.x * 256 + threadIdx.x; w < nwords; w += stride) {
     uint32_t v = words[w];
-    if (v) any[w] |= v;
     while (v) {
       const uint32_t j = __builtin_ctz(v);
       v &= v - 1;
@@ -139,66 +126,26 @@ __global__ __launch_bounds__(256) void k_set_or_slot(const uint32_t* __restrict_
 template <int W>
 __global__ __launch_bounds__(256) void k_set_put_slot(const uint32_t* __restrict__ words,
                                                       uint64_t m, uint32_t slot,
-                                                      void* __restrict__ set,
-                                                      uint32_t* __restrict__ any) {
+                                                      void* __restrict__ set) {
   const uint64_t ngroups = (m + 31) / 32;
   const uint64_t stride = (uint64_t)gridDim.x * 256;
   for (uint64_t g = (uint64_t)blockIdx.x * 256 + threadIdx.x; g < ngroups; g += stride) {
     const uint32_t v = words ? words[g] : 0u;
     const uint32_t valid = (uint32_t)min<uint64_t>(32, m - g * 32);
-    uint32_t u = 0;
     for (uint32_t j = 0; j < valid; ++j) {
       const uint64_t p = g * 32 + j;
       if constexpr (W == 32) {
         uint32_t* s = reinterpret_cast<uint32_t*>(set) + p;
-        const uint32_t nv = (*s & ~(1u << slot)) | (((v >> j) & 1u) << slot);
-        *s = nv;
-        u |= (uint32_t)(nv != 0) << j;
+        *s = (*s & ~(1u << slot)) | (((v >> j) & 1u) << slot);
       } else {
         uint64_t* s = reinterpret_cast<uint64_t*>(set) + p;
-        const uint64_t nv = (*s & ~(1ull << slot)) | ((uint64_t)((v >> j) & 1u) << slot);
-        *s = nv;
-        u |= (uint32_t)(nv != 0) << j;
+        *s = (*s & ~(1ull << slot)) | ((uint64_t)((v >> j) & 1u) << slot);
       }
     }
-    any[g] = u;
   }
 }
 
 constexpr uint32_t kSetProbeThreads = 64 * kSetWords;  // one 64-key hit word per wave
-#ifdef CB_EXPERIMENTS
-constexpr uint32_t kFlowThreads = 256;  // k_set_probe_flow: 4 waves per block
-constexpr uint32_t kFlowWaves = kFlowThreads / 64;
-#endif
-
-// set_key_mask for a 16-byte key already in registers (no union pre-test).
-template <int MODE, int W, bool SC>
-__device__ __forceinline__ typename std::conditional<W == 32, uint32_t, uint64_t>::type set_key_mask_u4(
-    const void* __restrict__ set, const uint4& kv, bool ok, const ModP& mp, const ZoneView& zv,
-    const BoundPrefix* zp) {
-  typedef typename std::conditional<W == 32, uint32_t, uint64_t>::type word_t;
-  typedef const __attribute__((address_space(1))) word_t* gptr;
-  const gptr sp = (gptr)set;
-  uint64_t pa = 0, pb = 0;
-  if (ok) key_positions_u4<MODE>(kv, mp, pa, pb);
-  const word_t va = ok ? sp[pa] : (word_t)0;
-  word_t vb;
-  if constexpr (!SC)
-    vb = ok ? sp[pb] : (word_t)0;
-  else
-    vb = va ? sp[pb] : (word_t)0;
-  word_t mask = va & vb;
-  word_t c = zv.gated ? mask & (word_t)zv.gated : (word_t)0;
-  if (c) {
-    const uint32_t kw[4] = {be32(kv.x), be32(kv.y), be32(kv.z), be32(kv.w)};
-    while (c) {
-      const uint32_t s = (uint32_t)__builtin_ctzll((uint64_t)c);
-      c &= c - 1;
-      if (cmp16(kw, zp[2 * s]) < 0 || cmp16(kw, zp[2 * s + 1]) > 0) mask &= ~((word_t)1 << s);
-    }
-  }
-  return mask;
-}
 
 // The wave's 64 keys' masks -> lane f holds slot f's 64-key hit word.
 template <int W, class word_t>
@@ -261,7 +208,6 @@ __device__ __forceinline__ void emit_positions(const PackSink& sink, const uint6
 // 40.9-41.1 us.)
 template <int KEYK, int MODE, int W, bool SC>
 __global__ __launch_bounds__(kSetProbeThreads) void k_set_probe(const void* __restrict__ set,
-                                                                const uint32_t* __restrict__ any,
                                                                 uint32_t used, KeySrc ks,
                                                                 uint64_t n, ModP mp, ZoneView zv,
                                                                 uint64_t* __restrict__ hits,
@@ -272,7 +218,7 @@ __global__ __launch_bounds__(kSetProbeThreads) void k_set_probe(const void* __re
   stage_zone_prefixes<KEYK, W>(zv, zp, kSetProbeThreads);  // issued alongside the key loads
   const uint64_t wbase = (uint64_t)blockIdx.x * kSetWords;
   const uint64_t k = (wbase + wave) * 64 + lane;
-  const auto mask = set_key_mask<KEYK, MODE, W, SC, true>(set, any, ks, k, k < n, mp, zv, zp);
+  const auto mask = set_key_mask<KEYK, MODE, W, SC, true>(set, ks, k, k < n, mp, zv, zp);
   const uint64_t mine = slot_words<W>(mask, used, lane);
   if (lane < used) hb[lane][wave] = mine;
   __syncthreads();
@@ -284,54 +230,6 @@ __global__ __launch_bounds__(kSetProbeThreads) void k_set_probe(const void* __re
   if (sink.pack) emit_positions(sink, hb, used, wbase, hwords);
 }
 
-#ifdef CB_EXPERIMENTS
-// Persistent form: a grid sized to the chip (blocks per CU x CUs), each wave
-// striding over 64-key hit words on its own, with no block barrier after the
-// start: a wave whose random reads came back early starts its next word at
-// once instead of waiting for the block's slowest wave, so the launch has no
-// block-round tail. Lane f stores slot f's word directly (one store
-// instruction per wave and word; the 8-byte pieces of a row's 128-byte
-// segment meet in L2).
-template <int KEYK, int MODE, int W, bool SC>
-__global__ __launch_bounds__(kFlowThreads) void k_set_probe_flow(const void* __restrict__ set,
-                                                                 const uint32_t* __restrict__ any,
-                                                                 uint32_t used, KeySrc ks,
-                                                                 uint64_t n, ModP mp, ZoneView zv,
-                                                                 uint64_t* __restrict__ hits,
-                                                                 uint64_t hwords) {
-  __shared__ BoundPrefix zp[2 * W];
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  stage_zone_prefixes<KEYK, W>(zv, zp, kFlowThreads);
-  if (KEYK == KEY_FIXED16 && zv.gated) __syncthreads();
-  const uint64_t nw = (n + 63) / 64;
-  const uint64_t stride = (uint64_t)gridDim.x * kFlowWaves;
-  uint64_t w = (uint64_t)blockIdx.x * kFlowWaves + wave;
-  if constexpr (KEYK == KEY_FIXED16) {
-    // software-pipelined: the next word's key load is in flight while this
-    // word's random set reads are outstanding
-    const uint4* kp = reinterpret_cast<const uint4*>(ks.bytes);
-    uint4 next = make_uint4(0, 0, 0, 0);
-    if (w < nw && w * 64 + lane < n) next = kp[w * 64 + lane];
-    for (; w < nw; w += stride) {
-      const uint64_t k = w * 64 + lane;
-      const uint4 kv = next;
-      const uint64_t kn = (w + stride) * 64 + lane;
-      if (w + stride < nw && kn < n) next = kp[kn];
-      const auto mask = set_key_mask_u4<MODE, W, SC>(set, kv, k < n, mp, zv, zp);
-      const uint64_t mine = slot_words<W>(mask, used, lane);
-      if (lane < used) hits[(uint64_t)lane * hwords + w] = mine;
-    }
-  } else {
-    for (; w < nw; w += stride) {
-      const uint64_t k = w * 64 + lane;
-      const auto mask = set_key_mask<KEYK, MODE, W, SC, false>(set, any, ks, k, k < n, mp, zv, zp);
-      const uint64_t mine = slot_words<W>(mask, used, lane);
-      if (lane < used) hits[(uint64_t)lane * hwords + w] = mine;
-    }
-  }
-}
-#endif  // CB_EXPERIMENTS
-
 inline uint32_t grid_cap(uint64_t items, uint32_t cap) {
   uint64_t g = (items + 255) / 256;
   if (g < 1) g = 1;
@@ -341,118 +239,68 @@ inline uint32_t grid_cap(uint64_t items, uint32_t cap) {
 }  // namespace
 
 hipError_t launch_set_build(const FilterPtrs& fp, uint32_t nf, uint64_t m, uint32_t width,
-                            void* set, uint32_t* any, hipStream_t s) {
+                            void* set, hipStream_t s) {
   if (!m) return hipSuccess;
   const uint64_t ngroups = (m + 31) / 32;
   ProfScope ps("k_set_build", s);
   if (width == 32)
     hipLaunchKernelGGL((k_set_build<32>), dim3(grid_cap(ngroups, 8192)), dim3(256), 0, s, fp, nf,
-                       ngroups, m, set, any);
+                       ngroups, m, set);
   else
     hipLaunchKernelGGL((k_set_build<64>), dim3(grid_cap(ngroups, 8192)), dim3(256), 0, s, fp, nf,
-                       ngroups, m, set, any);
+                       ngroups, m, set);
   return hipGetLastError();
 }
 
 hipError_t launch_set_or_slot(const uint32_t* words, uint64_t m, uint32_t slot, uint32_t width,
-                              void* set, uint32_t* any, hipStream_t s) {
+                              void* set, hipStream_t s) {
   if (!m) return hipSuccess;
   const uint64_t nw = (m + 31) / 32;
   ProfScope ps("k_set_or_slot", s);
   if (width == 32)
     hipLaunchKernelGGL((k_set_or_slot<32>), dim3(grid_cap(nw, 8192)), dim3(256), 0, s, words, nw,
-                       slot, set, any);
+                       slot, set);
   else
     hipLaunchKernelGGL((k_set_or_slot<64>), dim3(grid_cap(nw, 8192)), dim3(256), 0, s, words, nw,
-                       slot, set, any);
+                       slot, set);
   return hipGetLastError();
 }
 
 hipError_t launch_set_put_slot(const uint32_t* words, uint64_t m, uint32_t slot, uint32_t width,
-                               void* set, uint32_t* any, hipStream_t s) {
+                               void* set, hipStream_t s) {
   if (!m) return hipSuccess;
   const uint64_t ng = (m + 31) / 32;
   ProfScope ps("k_set_put_slot", s);
   if (width == 32)
     hipLaunchKernelGGL((k_set_put_slot<32>), dim3(grid_cap(ng, 8192)), dim3(256), 0, s, words, m,
-                       slot, set, any);
+                       slot, set);
   else
     hipLaunchKernelGGL((k_set_put_slot<64>), dim3(grid_cap(ng, 8192)), dim3(256), 0, s, words, m,
-                       slot, set, any);
+                       slot, set);
   return hipGetLastError();
 }
 
 template <int KK, int MM, int WW>
-static void set_probe(bool flow, const void* set, const uint32_t* any, uint32_t used, const KeySrc& ks,
-                      uint64_t n, const ModP& mp, const ZoneView& zv, uint64_t* hits, uint64_t hwords,
-                      uint32_t grid, hipStream_t s, const PackSink& sink) {
-#ifdef CB_EXPERIMENTS
-  if (flow) {
-    hipLaunchKernelGGL((k_set_probe_flow<KK, MM, WW, true>), dim3(grid), dim3(kFlowThreads), 0, s, set, any,
-                       used, ks, n, mp, zv, hits, hwords);
-    return;
-  }
-#else
-  (void)flow;
-#endif
+static void set_probe(const void* set, uint32_t used, const KeySrc& ks, uint64_t n, const ModP& mp,
+                      const ZoneView& zv, uint64_t* hits, uint64_t hwords, uint32_t grid, hipStream_t s,
+                      const PackSink& sink) {
   // the reference's short-circuit (src/bloom.rs:50): set[b] only where set[a] != 0
-  hipLaunchKernelGGL((k_set_probe<KK, MM, WW, true>), dim3(grid), dim3(kSetProbeThreads), 0, s, set, any, used,
-                     ks, n, mp, zv, hits, hwords, sink);
+  hipLaunchKernelGGL((k_set_probe<KK, MM, WW, true>), dim3(grid), dim3(kSetProbeThreads), 0, s, set, used, ks, n,
+                     mp, zv, hits, hwords, sink);
 }
-
-#ifdef CB_EXPERIMENTS
-// Compute units of the current device (cached per device).
-static uint32_t device_cus() {
-  static uint32_t cus[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-  if (!cus[dev]) {
-    int v = 0;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-    cus[dev] = (uint32_t)v;
-  }
-  return cus[dev];
-}
-#endif
 
 hipError_t launch_set_probe(int keyk, int mode, uint32_t width, const void* set,
-                            const uint32_t* any, uint32_t used, const KeySrc& ks, uint64_t n,
+                            uint32_t used, const KeySrc& ks, uint64_t n,
                             const ModP& mp, const ZoneView* zones, uint64_t* hits,
                             uint64_t hwords, hipStream_t s, const PackSink* sink) {
   if (!n || !used) return hipSuccess;
   const PackSink nosink{nullptr, 0, nullptr, 0};
   const ZoneView zv = zones ? *zones : ZoneView{nullptr, nullptr, nullptr, 0};
   const uint64_t nw = (n + 63) / 64;
-  uint32_t grid = (uint32_t)((nw + kSetWords - 1) / kSetWords);
-  bool use_any = false, flow = false;
-#ifdef CB_EXPERIMENTS
-  // A/B knobs, compiled only into experiment builds (make EXTRA=-DCB_EXPERIMENTS):
-  // CB_SET_ANY=1 the union pre-test (measured on C3: 52.8 vs 40.0 us, the 2
-  // extra random reads per key into any[] cost as much as the set reads they
-  // avoid); CB_SET_FLOW=1 the persistent k_set_probe_flow (38.6-39.3 us, no
-  // better; slower at the C5 shape), CB_SET_FLOW_BPC its blocks per CU.
-  static const bool env_any = [] {
-    const char* v = getenv("CB_SET_ANY");
-    return v && v[0] == '1';
-  }();
-  static const int env_flow_bpc = [] {
-    const char* v = getenv("CB_SET_FLOW");
-    if (!(v && v[0] == '1')) return 0;
-    const char* b = getenv("CB_SET_FLOW_BPC");
-    return b && atoi(b) > 0 ? atoi(b) : 8;
-  }();
-  use_any = env_any;
-  flow = env_flow_bpc && !use_any && !sink;  // no union pre-test or pack in the flow form
-  if (flow) {
-    const uint64_t want = (nw + kFlowWaves - 1) / kFlowWaves;
-    const uint64_t cap = (uint64_t)device_cus() * (uint32_t)env_flow_bpc;
-    grid = (uint32_t)(want < cap ? want : cap);
-  }
-#endif
+  const uint32_t grid = (uint32_t)((nw + kSetWords - 1) / kSetWords);
   ProfScope ps(zv.gated ? "k_set_probe_gated" : "k_set_probe", s);
   CB_SET_DISPATCH(keyk, mode, width,
-                  (set_probe<KK, MM, WW>(flow, set, use_any ? any : nullptr, used, ks, n, mp, zv, hits, hwords,
-                                         grid, s, sink ? *sink : nosink)));
+                  (set_probe<KK, MM, WW>(set, used, ks, n, mp, zv, hits, hwords, grid, s, sink ? *sink : nosink)));
   return hipGetLastError();
 }
 

@@ -9,16 +9,14 @@
 namespace cb {
 
 // slots 0..nf-1 := the packed filters fp.w[0..nf-1] (all of size m); other slots zero.
-// Every update also maintains any[m/32] (packed): bit p = (set[p] != 0), the
-// union filter the probe tests first.
 hipError_t launch_set_build(const FilterPtrs& fp, uint32_t nf, uint64_t m, uint32_t width,
-                            void* set, uint32_t* any, hipStream_t s);
+                            void* set, hipStream_t s);
 // slot |= packed filter words (slot known all-zero: sparse update).
 hipError_t launch_set_or_slot(const uint32_t* words, uint64_t m, uint32_t slot, uint32_t width,
-                              void* set, uint32_t* any, hipStream_t s);
+                              void* set, hipStream_t s);
 // slot := packed filter words (words == nullptr clears the slot): full pass.
 hipError_t launch_set_put_slot(const uint32_t* words, uint64_t m, uint32_t slot, uint32_t width,
-                               void* set, uint32_t* any, hipStream_t s);
+                               void* set, hipStream_t s);
 // The probe block: kSetWords hit words (64 keys each) of every slot.
 constexpr uint32_t kSetWords = 16;
 inline uint64_t set_probe_blocks(uint64_t n) { return ((n + 63) / 64 + kSetWords - 1) / kSetWords; }
@@ -38,9 +36,9 @@ struct PackSink {
 
 // hits[slot][ceil(n/64)] for slots 0..used-1. zones (nullable): the
 // SsTable::get zone gate, applied to the slots in zones->gated. sink
-// (nullable): also write the hit positions as a pack (the block form only).
+// (nullable): also write the hit positions as a pack.
 hipError_t launch_set_probe(int keyk, int mode, uint32_t width, const void* set,
-                            const uint32_t* any, uint32_t used, const KeySrc& ks, uint64_t n,
+                            uint32_t used, const KeySrc& ks, uint64_t n,
                             const ModP& mp, const ZoneView* zones, uint64_t* hits,
                             uint64_t hwords, hipStream_t s, const PackSink* sink = nullptr);
 

@@ -22,10 +22,10 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdlib>
 
 #include "blockscan.hpp"
 #include "kernels.hpp"
+#include "knobs.hpp"
 #include "profile.hpp"
 
 // Phase stamps for diagnostics (tools/ubench_build.hip defines CB_STAMPS and
@@ -241,6 +241,9 @@ constexpr uint32_t kPartThreads = 256;
 // Fewer, larger tiles (~256 for C2) and larger blocks make the average run
 // ~32 entries = one 128-B line.
 constexpr uint32_t kBuildNT = 1024;
+// Store cache policy of the build's two outputs: bit 0 write-through
+// partition entries, bit 1 non-temporal tile write-back.
+constexpr uint32_t kBuildStores = CB_BUILD_STORES;
 
 // A 16-byte key's two positions packed as partition entries ((bin << 20) |
 // offset in the bin, bins of 2^tb bits), 0xFFFFFFFF for both when !live.
@@ -276,10 +279,9 @@ __device__ __forceinline__ void pack_positions(const uint4& kv, bool live, const
 // LDS and out to `out` as one contiguous region. Barriers inside; the block's
 // LDS is free again when it returns except for the final store's reads of
 // `stage` (the caller's next LDS write must follow a barrier).
-// pol: the store policy bits (build_stores(): bit 0 write-through entries).
 template <int KPT, typename E>
 __device__ __forceinline__ void part_phases(const uint32_t (&q)[2 * KPT], uint32_t T, uint32_t* smem,
-                                            uint32_t* __restrict__ srow, E* __restrict__ out, uint32_t pol) {
+                                            uint32_t* __restrict__ srow, E* __restrict__ out) {
   constexpr uint32_t NT = kBuildNT, C = NT * KPT;
   constexpr uint32_t kNone = 0xFFFFFFFFu;
   const uint32_t Tp = (T + 4) & ~3u;
@@ -314,9 +316,7 @@ __device__ __forceinline__ void part_phases(const uint32_t (&q)[2 * KPT], uint32
   // kernel's end has no dirty L2 lines to write back, and the tile pass (on
   // other XCDs) still finds them there; C2 on four lanes 101 -> 105-107 G
   // keys/s (non-temporal stores instead made the tile pass's reads slower)
-  if (pol & 4u) {  // (bit 2: non-temporal entries)
-    for (uint32_t i = tid; i < n4; i += NT) store16_nt(reinterpret_cast<uint4*>(out) + i, reinterpret_cast<const uint4*>(stage)[i]);
-  } else if (pol & 1u) {
+  if constexpr (kBuildStores & 1u) {
     const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(out, 0, 2 * C * sizeof(E), 0x00020000);
     for (uint32_t i = tid; i < n4; i += NT) store16_wt(r, i * 16, reinterpret_cast<const uint4*>(stage)[i]);
   } else {
@@ -334,7 +334,7 @@ template <int KEYK, int MODE, int KPT, typename E = uint32_t>
 __global__ __launch_bounds__(kBuildNT) void k_build_part(BuildBatch bb, ModP mp, uint32_t tb,
                                                          uint32_t T,
                                                          uint32_t* __restrict__ seg_all,
-                                                         void* __restrict__ ent_all, uint32_t pol) {
+                                                         void* __restrict__ ent_all) {
   constexpr uint32_t NT = kBuildNT, C = NT * KPT;
   static_assert(sizeof(E) == 4 || sizeof(E) == 2, "entry type");
   const KeySrc ks = bb.ks[blockIdx.y];
@@ -384,7 +384,7 @@ __global__ __launch_bounds__(kBuildNT) void k_build_part(BuildBatch bb, ModP mp,
       }
     }
   }
-  part_phases<KPT, E>(q, T, smem, seg + (size_t)blockIdx.x * (T + 1), ent + (size_t)blockIdx.x * (2 * C), pol);
+  part_phases<KPT, E>(q, T, smem, seg + (size_t)blockIdx.x * (T + 1), ent + (size_t)blockIdx.x * (2 * C));
 }
 
 // Wave w owns partition blocks b = w + NW*u. Per group of 16: lanes 0..15
@@ -392,14 +392,13 @@ __global__ __launch_bounds__(kBuildNT) void k_build_part(BuildBatch bb, ModP mp,
 // run's start and length to the whole wave, and the wave issues the 16 run
 // loads back to back (lane i = entry i): two dependent memory round trips per
 // group and no LDS run table or barrier before the ORs.
-// pol: the store policy bits (build_stores(): bit 1 non-temporal write-back).
-template <int G, int R, uint32_t NT = kBuildNT>
-__global__ __launch_bounds__(NT) void k_build_tile(BuildBatch bb, uint32_t tb, uint32_t T,
+template <int G, int R>
+__global__ __launch_bounds__(kBuildNT) void k_build_tile(BuildBatch bb, uint32_t tb, uint32_t T,
                                                          const uint32_t* __restrict__ seg_all,
                                                          uint32_t nblk,
                                                          const uint32_t* __restrict__ ent_all,
-                                                         uint32_t estride, uint32_t pol) {
-  constexpr uint32_t NW = NT / 64;
+                                                         uint32_t estride) {
+  constexpr uint32_t NT = kBuildNT, NW = NT / 64;
   static_assert(G <= 64, "one lane per run bound");
   uint32_t* __restrict__ words = bb.words[blockIdx.y];
   const bool fresh = (bb.fresh >> blockIdx.y) & 1ull;
@@ -479,7 +478,7 @@ __global__ __launch_bounds__(NT) void k_build_tile(BuildBatch bb, uint32_t tb, u
   // no L2 lines to write back at the kernel's end (tile pass alone 8.8 ->
   // 7.5 us, C2 on four lanes 97.8 -> 101 G keys/s; write-through measured
   // the same here)
-  if (pol & 2u)
+  if constexpr (kBuildStores & 2u)
     for (uint32_t i = tid; i < tw / 4; i += NT) store16_nt(gt + i, lt[i]);
   else
     for (uint32_t i = tid; i < tw / 4; i += NT) gt[i] = lt[i];
@@ -499,7 +498,7 @@ __global__ __launch_bounds__(NT) void k_build_tile_sub(BuildBatch bb, uint32_t t
                                                        const uint32_t* __restrict__ seg_all,
                                                        uint32_t nblk,
                                                        const uint16_t* __restrict__ ent_all,
-                                                       uint32_t estride, uint32_t pol) {
+                                                       uint32_t estride) {
   constexpr uint32_t NW = NT / 64, S = 1u << SUB, NB = S + 1;
   static_assert(G * NB <= 64, "one lane per bound");
   uint32_t* __restrict__ words = bb.words[blockIdx.y];
@@ -580,7 +579,7 @@ __global__ __launch_bounds__(NT) void k_build_tile_sub(BuildBatch bb, uint32_t t
     }
   }
   __syncthreads();
-  if (pol & 2u)
+  if constexpr (kBuildStores & 2u)
     for (uint32_t i = tid; i < tw / 4; i += NT) store16_nt(gt + i, lt[i]);
   else
     for (uint32_t i = tid; i < tw / 4; i += NT) gt[i] = lt[i];
@@ -651,10 +650,6 @@ __global__ __launch_bounds__(kPartThreads) void k_part_probe(KeySrc ks, uint64_t
 
 constexpr uint32_t kTileProbeThreads = 512;
 
-// Timing-only experiment switches for k_tile_probe (CB_PROBE_XFLAGS; results
-// are wrong when set — bench attribution only, never set in production).
-constexpr uint32_t kXSkipGather = 1, kXSkipStream = 2, kXSkipStore = 4;
-
 // Probe one tile against up to 32 filters (group blockIdx.y). Each filter's
 // tile is streamed HBM -> registers -> LDS through a D-deep register ring, so
 // D tiles are in flight while the current one is tested. Bit a is tested in
@@ -665,7 +660,7 @@ template <int EPT, int RPT, int D>
 __global__ __launch_bounds__(kTileProbeThreads) void k_tile_probe(
     FilterPtrs fp, uint32_t nf, uint32_t tb, uint32_t T, const uint32_t* __restrict__ seg,
     uint32_t nblk, const uint2* __restrict__ ent, uint32_t C, uint64_t n,
-    uint32_t* __restrict__ masks, uint32_t xflags) {
+    uint32_t* __restrict__ masks) {
   constexpr uint32_t NT = kTileProbeThreads;
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
   const uint32_t tw = 1u << (tb - 5);  // == RPT * 4 * NT
@@ -688,7 +683,7 @@ __global__ __launch_bounds__(kTileProbeThreads) void k_tile_probe(
   // through address-space-1 pointers (global_load, counted vmcnt waits).
   u32x4 r0[RPT], r1[RPT], r2[RPT], r3[RPT];
 #define TP_FETCH(R, F)                                                        \
-  if (!(xflags & kXSkipStream)) {                                             \
+  {                                                                           \
     const gptr_u4 src = (gptr_u4)(fp.w[f0 + (F)] + (size_t)t * tw);           \
     _Pragma("unroll") for (int q = 0; q < RPT; ++q) R[q] = src[tid + q * NT]; \
   }
@@ -764,7 +759,7 @@ __global__ __launch_bounds__(kTileProbeThreads) void k_tile_probe(
 #pragma unroll
     for (int i = 0; i < EPT; ++i) {
       mask[i] = 0;
-      x[i] = ((uint32_t)i < cnt && !(xflags & kXSkipGather)) ? am[i] : 0u;
+      x[i] = (uint32_t)i < cnt ? am[i] : 0u;
     }
     for (;;) {
       uint32_t any = 0, v[EPT];
@@ -783,11 +778,9 @@ __global__ __launch_bounds__(kTileProbeThreads) void k_tile_probe(
         }
       }
     }
-    if (!(xflags & kXSkipStore)) {
 #pragma unroll
-      for (int i = 0; i < EPT; ++i)
-        if ((uint32_t)i < cnt) mg[slot[i]] = mask[i];
-    }
+    for (int i = 0; i < EPT; ++i)
+      if ((uint32_t)i < cnt) mg[slot[i]] = mask[i];
   }
 #undef TP_FETCH_FIRST
 #undef TP_FETCH
@@ -947,20 +940,9 @@ static uint32_t fit_tiles(uint64_t m, int64_t tb, int64_t hi) {
   return (uint32_t)tb;
 }
 
-// Tuning overrides, compiled only into experiment builds (make
-// EXTRA=-DCB_EXPERIMENTS): CB_PROBE_TB / CB_BUILD_TB fix the tile bits,
-// CB_PROBE_KPT / CB_BUILD_KPT the partition keys per thread, CB_BUILD_STORES
-// the build's store policy, CB_PROBE_XFLAGS the tile probe's variant bits.
-// The shipped library always takes the defaults.
-static int env_int(const char* name, int dflt) {
-#ifdef CB_EXPERIMENTS
-  const char* v = getenv(name);
-  return v && *v ? atoi(v) : dflt;
-#else
-  (void)name;
-  return dflt;
-#endif
-}
+// Tuning overrides (knobs.hpp; the shipped library always takes the
+// defaults): CB_PROBE_TB / CB_BUILD_TB fix the tile bits, CB_PROBE_KPT /
+// CB_BUILD_KPT the partition keys per thread.
 
 TilePlan plan_build(uint64_t m, uint64_t n, uint32_t nb) {
   // ~256 tiles per launch over the whole batch, each as large as the 64 KiB
@@ -968,8 +950,8 @@ TilePlan plan_build(uint64_t m, uint64_t n, uint32_t nb) {
   // 1024-thread partition blocks of up to 4096 keys, fewer keys per thread
   // only while that leaves under 256 blocks in the launch.
   TilePlan p{};
-  static const int env_tb = env_int("CB_BUILD_TB", 0);
-  static const int env_kpt = env_int("CB_BUILD_KPT", 0);
+  static const int env_tb = knob_int("CB_BUILD_TB", 0);
+  static const int env_kpt = knob_int("CB_BUILD_KPT", 0);
   if (nb < 1) nb = 1;
   const uint64_t want_tiles = nb >= 256 ? 1 : 256 / nb;
   int64_t tb = clamp64((int64_t)ilog2_floor(m > want_tiles ? m / want_tiles : 1), kMinTileBits,
@@ -992,7 +974,7 @@ TilePlan plan_build(uint64_t m, uint64_t n, uint32_t nb) {
   // workgroups, four per CU instead of two 1024-thread ones on 2^19-bit
   // tiles: C4 141 -> 128-131 us per step on one lane, 147-151 -> 139-141 on
   // three (profiles/c4_sub_r04.json).
-  static const int env_sub = env_int("CB_BUILD_SUB", -1);
+  static const int env_sub = knob_int("CB_BUILD_SUB", -1);
   p.sub = 0;
   // (CB_BUILD_SUB=1, experiment builds: every build of tb >= 17 takes them)
   if (env_sub != 0 && p.tb >= 17 && ((nb >= 8 && 2ull * p.C > 48ull * p.T) || env_sub == 1)) {
@@ -1013,14 +995,14 @@ TilePlan plan_probe(uint64_t m, uint64_t n) {
   const uint64_t want = n ? (m * 4096ull) / n : m;
   int64_t tb2 = (int64_t)ilog2_floor(want ? want : 1);
   int64_t tb = clamp64(tb1 < tb2 ? tb1 : tb2, kMinProbeTileBits, kMaxProbeTileBits);
-  static const int env_tb = env_int("CB_PROBE_TB", 0);
+  static const int env_tb = knob_int("CB_PROBE_TB", 0);
   if (env_tb) tb = clamp64(env_tb, kMinProbeTileBits, kMaxProbeTileBits);
   p.tb = fit_tiles(m, tb, kMaxProbeTileBits);
   p.T = (uint32_t)((m + (1ull << p.tb) - 1) >> p.tb);
   // Longer runs per (block, tile) with C = 2048 once that still leaves >= 512
   // partition blocks; never more than 4096 blocks (the host chunks keys).
   p.kpt = n >= 512ull * 2048 ? 8 : 4;
-  static const int env_kpt = env_int("CB_PROBE_KPT", 0);
+  static const int env_kpt = knob_int("CB_PROBE_KPT", 0);
   if (env_kpt == 4 || env_kpt == 8) p.kpt = env_kpt;
   p.C = kPartThreads * p.kpt;
   p.nblk = (uint32_t)((n + p.C - 1) / p.C);
@@ -1089,26 +1071,18 @@ static void part_probe(const TilePlan& p, const KeySrc& ks, uint64_t n, const Mo
                      mp, p.tb, p.T, seg, ent, lkey);
 }
 
-// Store cache policy of the build's two outputs (CB_BUILD_STORES, default
-// 3): bit 0 write-through partition entries, bit 1 non-temporal tile
-// write-back.
-static uint32_t build_stores() {
-  static const uint32_t v = (uint32_t)env_int("CB_BUILD_STORES", 3);
-  return v;
-}
-
 template <int KK, int MM, int KPT>
 static void build_part(const TilePlan& p, const BuildBatch& bb, uint32_t nb, const ModP& mp,
                        uint32_t* seg, uint32_t* ent, size_t lds, hipStream_t s) {
   if (p.sub) {  // 16-bit entries binned by 2^16-bit sub-tile
     allow_lds(k_build_part<KK, MM, KPT, uint16_t>, lds);
     hipLaunchKernelGGL((k_build_part<KK, MM, KPT, uint16_t>), dim3(p.nblk, nb), dim3(kBuildNT), lds, s, bb, mp,
-                       16u, p.T << p.sub, seg, ent, build_stores());
+                       16u, p.T << p.sub, seg, ent);
     return;
   }
   allow_lds(k_build_part<KK, MM, KPT>, lds);
   hipLaunchKernelGGL((k_build_part<KK, MM, KPT>), dim3(p.nblk, nb), dim3(kBuildNT), lds, s, bb, mp,
-                     p.tb, p.T, seg, ent, build_stores());
+                     p.tb, p.T, seg, ent);
 }
 
 hipError_t launch_build_batch(int keyk, int mode, const BuildBatch& bb, uint32_t nb,
@@ -1138,13 +1112,13 @@ hipError_t launch_build_batch(int keyk, int mode, const BuildBatch& bb, uint32_t
     if (p.sub == 2) {  // 2^18-bit tiles: 512-thread workgroups, four per CU
       allow_lds(k_build_tile_sub<8, 2, 2, 512>, lds2);
       hipLaunchKernelGGL((k_build_tile_sub<8, 2, 2, 512>), dim3(p.T, nb), dim3(512), lds2, s, bb, p.tb, p.T, seg,
-                         p.nblk, e16, 2 * p.C, build_stores());
+                         p.nblk, e16, 2 * p.C);
       return hipGetLastError();
     }
 #define CB_TILE_SUB(SUBV)                                                                                 \
   allow_lds(k_build_tile_sub<4, 2, SUBV>, lds2);                                                         \
   hipLaunchKernelGGL((k_build_tile_sub<4, 2, SUBV>), dim3(p.T, nb), dim3(kBuildNT), lds2, s, bb, p.tb, p.T, seg, \
-                     p.nblk, e16, 2 * p.C, build_stores())
+                     p.nblk, e16, 2 * p.C)
     if (p.sub == 1) {
       CB_TILE_SUB(1);
     } else {
@@ -1155,23 +1129,14 @@ hipError_t launch_build_batch(int keyk, int mode, const BuildBatch& bb, uint32_t
   }
   // entries per (partition block, tile): 2 C / T on average (tiles of one
   // filter); two rounds of run loads once that passes ~3/4 of a wave
-#ifdef CB_EXPERIMENTS
-  static const int tile_nt = env_int("CB_BUILD_TILE_NT", 1024);  // 512: half-size tile workgroups
-  if (tile_nt == 512) {
-    allow_lds(k_build_tile<8, 2, 512>, lds2);
-    hipLaunchKernelGGL((k_build_tile<8, 2, 512>), dim3(p.T, nb), dim3(512), lds2, s, bb, p.tb, p.T, seg, p.nblk,
-                       ent, 2 * p.C, build_stores());
-    return hipGetLastError();
-  }
-#endif
   if (2ull * p.C > 48ull * p.T) {
     allow_lds(k_build_tile<8, 2>, lds2);
     hipLaunchKernelGGL((k_build_tile<8, 2>), dim3(p.T, nb), dim3(kBuildNT), lds2, s, bb, p.tb, p.T, seg, p.nblk,
-                       ent, 2 * p.C, build_stores());
+                       ent, 2 * p.C);
   } else {
     allow_lds(k_build_tile<16, 1>, lds2);
     hipLaunchKernelGGL((k_build_tile<16, 1>), dim3(p.T, nb), dim3(kBuildNT), lds2, s, bb, p.tb, p.T, seg,
-                       p.nblk, ent, 2 * p.C, build_stores());
+                       p.nblk, ent, 2 * p.C);
   }
   return hipGetLastError();
 }
@@ -1207,13 +1172,12 @@ template <int RPT>
 static hipError_t tile_probe(const FilterPtrs& fp, uint32_t nf, uint64_t n, const TilePlan& p,
                              const uint32_t* seg, const uint2* ent, uint32_t* masks, size_t lds,
                              uint32_t G, hipStream_t s) {
-  static const uint32_t xflags = (uint32_t)env_int("CB_PROBE_XFLAGS", 0);
   // The instantiation must cover the tile exactly: RPT uint4 per thread.
   if ((1u << (p.tb - 5)) != (uint32_t)RPT * 4u * kTileProbeThreads) return hipErrorInvalidValue;
   constexpr int D = RPT >= 4 ? 2 : 4;  // 32-64 KiB of tiles in flight per workgroup
   allow_lds(k_tile_probe<8, RPT, D>, lds);
   hipLaunchKernelGGL((k_tile_probe<8, RPT, D>), dim3(p.T, G), dim3(kTileProbeThreads), lds, s, fp,
-                     nf, p.tb, p.T, seg, p.nblk, ent, p.C, n, masks, xflags);
+                     nf, p.tb, p.T, seg, p.nblk, ent, p.C, n, masks);
   return hipGetLastError();
 }
 

@@ -11,8 +11,6 @@
 
 namespace cb {
 
-typedef const __attribute__((address_space(1))) uint32_t* gsp32;
-
 // One key's answer for every slot: bit s of the result = slot s's
 // may_contain (and, for gated slots, its ZoneMap::contains). SC = the
 // reference's `&&` short-circuit (src/bloom.rs:50): set[b] is read only when
@@ -29,8 +27,8 @@ typedef const __attribute__((address_space(1))) uint32_t* gsp32;
 // key's loads have issued (callers where every thread calls this exactly once).
 template <int KEYK, int MODE, int W, bool SC, bool ZP_SYNC>
 __device__ __forceinline__ typename std::conditional<W == 32, uint32_t, uint64_t>::type set_key_mask(
-    const void* __restrict__ set, const uint32_t* __restrict__ any, const KeySrc& ks, uint64_t k,
-    bool ok, const ModP& mp, const ZoneView& zv, const BoundPrefix* zp) {
+    const void* __restrict__ set, const KeySrc& ks, uint64_t k, bool ok, const ModP& mp, const ZoneView& zv,
+    const BoundPrefix* zp) {
   typedef typename std::conditional<W == 32, uint32_t, uint64_t>::type word_t;
   typedef const __attribute__((address_space(1))) word_t* gptr;
   const gptr sp = (gptr)set;
@@ -43,15 +41,6 @@ __device__ __forceinline__ typename std::conditional<W == 32, uint32_t, uint64_t
     } else {
       key_positions<KEYK, MODE>(ks, k, mp, pa, pb);
     }
-  }
-  // Union pre-test: any[p] = (set[p] != 0) is the Bloom filter of every
-  // slot's keys (m bits, L2/MALL-resident). A key whose a or b bit is clear
-  // there is absent from every slot and skips both set reads.
-  if (any) {
-    const gsp32 ap = (gsp32)any;
-    const uint32_t ua = ok ? ap[pa >> 5] : 0u;
-    const uint32_t ub = ok ? ap[pb >> 5] : 0u;
-    ok = ok && ((ua >> (pa & 31)) & (ub >> (pb & 31)) & 1u);
   }
   const word_t va = ok ? sp[pa] : (word_t)0;
   word_t vb;

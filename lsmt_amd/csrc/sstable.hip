@@ -14,10 +14,10 @@
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
-#include <cstdlib>
 #include <cstring>
 
 #include "blockscan.hpp"
+#include "knobs.hpp"
 #include "profile.hpp"
 #include "setmask.hpp"
 #include "sstable.hpp"
@@ -911,7 +911,7 @@ __global__ __launch_bounds__(kNT, 6) void k_set_get_many(const void* __restrict_
   // the whole search's state live across the gate: 256 VGPRs, 1 wave/SIMD)
   const Query q = make_query<KEYK>(ks, k < n ? k : 0);
   store_views(vr, nt, stv);  // barrier: views, slots and zone prefixes staged
-  const auto mask = set_key_mask<KEYK, MODE, W, true, false>(set, nullptr, ks, k, k < n, mp, zv, zp);
+  const auto mask = set_key_mask<KEYK, MODE, W, true, false>(set, ks, k, k < n, mp, zv, zp);
   uint64_t cand0 = 0;
   if (slots) {
     for (uint32_t i = 0; i < nt; ++i) cand0 |= (((uint64_t)mask >> sslot[i]) & 1ull) << i;
@@ -977,11 +977,7 @@ __global__ __launch_bounds__(kNT) void k_wide_screen(const TableView* __restrict
 // tables of m = 1024); 16 doubles the scratch spill (36 -> 72 B per lane).
 // With the screen (round 5) the batch no longer matters: 8 / 4 / 2 at once
 // measured 2.145 / 2.140 / 2.139 G gets/s, the same VGPRs (experiment builds).
-#if defined(CB_EXPERIMENTS) && defined(CB_WIDE_SCREEN_BATCH)
 constexpr uint32_t kScreen = CB_WIDE_SCREEN_BATCH;
-#else
-constexpr uint32_t kScreen = 8;
-#endif
 // (Round 4, before the screen: five waves per SIMD at its natural 96 VGPRs;
 // forcing six, 80 VGPRs with 112 B of scratch per lane, measured 606-617
 // against 782-804 M gets/s.)
@@ -991,11 +987,7 @@ constexpr uint32_t kScreen = 8;
 // The walk's workgroup: kWideNT keys (two 256-key tiles of the value scan);
 // a group's views and maps are staged once per workgroup, so 512 keys per
 // workgroup halve the staging's L2 requests per lookup against 256.
-#if defined(CB_EXPERIMENTS) && defined(CB_WIDE_THREADS)
 constexpr uint32_t kWideNT = CB_WIDE_THREADS;
-#else
-constexpr uint32_t kWideNT = 512;
-#endif
 static_assert(kWideNT % kNT == 0 && kWideNT / kNT <= 4, "up to four value tiles per workgroup");
 template <int KEYK, int MODE>
 __global__ __launch_bounds__(kWideNT, 4) void k_wide_get_many(const uint64_t* __restrict__ set, uint32_t R, ModP mp,
@@ -1277,9 +1269,6 @@ constexpr uint32_t kDecodeLds = 16384;  // staged output bytes per block
 // are one contiguous output range; when it fits in LDS, lanes decode into LDS
 // and the block writes the range with aligned dword stores, else lanes write
 // their bytes directly.
-#ifdef CB_EXPERIMENTS
-__constant__ int g_b64_x;
-#endif
 // (Two adjacent keys per thread, so all of a 1M-key batch's value loads are
 // in flight in one round, measured slower: read path 14.3 against 14.8-14.9 G
 // gets/s, wide fan-out 1.97-2.00 against 2.04-2.06; experiment r05_b64kpt, HISTORY.md.)
@@ -1320,13 +1309,7 @@ __global__ __launch_bounds__(kNT) void k_b64_decode(const uint64_t* __restrict__
   // (RAW: the total is not known yet, so the chars load whenever there is an
   // output; a total above cap then leaves them unused)
   const bool want = out && (RAW || vn <= cap);
-#ifdef CB_EXPERIMENTS
-  // (timing-only A/B, wrong bytes: CB_B64_X bit 0 skips the value loads)
-  if (want && small && !(g_b64_x & 1)) b64_small_load(src, dl, sv);
-  if (g_b64_x & 1) sv = SmallB64{{0x41414141u, 0x41414141u, 0x41414141u, 0x41414141u, 0x41414141u, 0x41414141u, 0x41414141u}, 0};
-#else
   if (want && small) b64_small_load(src, dl, sv);
-#endif
   uint64_t total, pre;
   if constexpr (RAW) {
     uint64_t before = 0, all = 0;
@@ -1646,14 +1629,6 @@ hipError_t launch_tile_scan(uint64_t* tsum, uint64_t nt, uint64_t* total_out, hi
 
 hipError_t launch_b64_decode(const uint64_t* vsrc, const uint64_t* dlen, const uint64_t* tsum,
                              uint64_t n, uint64_t* voff, uint8_t* out, uint64_t cap, hipStream_t s, bool raw) {
-#ifdef CB_EXPERIMENTS
-  static const int env_x = [] {
-    const int x = getenv("CB_B64_X") ? atoi(getenv("CB_B64_X")) : 0;
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_b64_x), &x, sizeof(x));
-    return x;
-  }();
-  (void)env_x;
-#endif
   if (!n) return hipSuccess;
   const uint32_t nb = blocks_for(n, kNT);
   if (raw && nb > kRawTiles) return hipErrorInvalidValue;

@@ -413,42 +413,30 @@ def test_filterset_c3_golden(gpu, golden):
     assert sha(s2.probe(look).astype("<u8")) == g["hits_sha256"]
 
 
-_UNION_SCRIPT = r"""
-import sys, numpy as np
-sys.path.insert(0, sys.argv[1])
-import lsmt_amd
-from lsmt_amd import workload
-from oracle import oracle
-m = (1 << 20) + 9
-fs, rs = [], []
-for f in range(5):
-    k = workload.key_range(700 + f, 6000)
-    g = lsmt_amd.BloomFilter(m); g.insert_batch(k); fs.append(g)
-    o = oracle.OracleFilter(m); o.insert_fixed(k); rs.append(o)
-look = workload.probe_lookups(30000, 5, 6000, seed_base=700, absent_seed=995)
-s = lsmt_amd.FilterSet.from_filters(fs[:3])          # union built by the transpose
-assert np.array_equal(s.probe(look), oracle.probe_fixed(rs[:3], look))
-s.assign(3, fs[3]); s.assign(4, fs[4])              # union kept by the sparse OR
-assert np.array_equal(s.probe(look), oracle.probe_fixed(rs, look))
-s.clear_slot(0); s.assign(1, fs[4])                  # union recomputed by the dense rewrite
-z = oracle.OracleFilter(m)
-assert np.array_equal(s.probe(look), oracle.probe_fixed([z, rs[4], rs[2], rs[3], rs[4]], look))
-print("union ok")
-"""
-
-
-def test_filterset_union_mode(gpu):
-    # CB_SET_ANY=1 (opt-in union pre-test) is read once per process, and only
-    # by experiment builds (-DCB_EXPERIMENTS); the shipped library ignores it,
-    # so there this checks that the set's union upkeep leaves answers exact
-    import os
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, CB_SET_ANY="1")
-    r = subprocess.run([sys.executable, "-c", _UNION_SCRIPT, root], env=env, capture_output=True,
-                       text=True, timeout=300)
-    assert r.returncode == 0 and "union ok" in r.stdout, r.stdout + r.stderr
+@pytest.mark.parametrize("nf0", [3, 37], ids=["w32", "w64"])
+def test_filterset_updates_match_oracle(gpu, nf0):
+    # every way a set's words change (the transpose build, the sparse OR into
+    # an empty slot, the dense rewrite of a slot that holds bits, clear_slot)
+    # leaves the probe equal to the oracle; m = 2^20 + 9: a ragged last group.
+    # nf0 = 3 takes the 32-slot kernels, nf0 = 37 the 64-slot ones.
+    m = (1 << 20) + 9
+    nf = nf0 + 2
+    fs, rs = [], []
+    for f in range(nf):
+        g, o = build_pair(gpu, m, workload.key_range(700 + f, 6000))
+        fs.append(g)
+        rs.append(o)
+    look = workload.probe_lookups(30000, nf, 6000, seed_base=700, absent_seed=995)
+    s = gpu.FilterSet.from_filters(fs[:nf0])  # the transpose
+    assert s.width == (32 if nf0 <= 32 else 64)
+    assert np.array_equal(s.probe(look), oracle.probe_fixed(rs[:nf0], look))
+    s.assign(nf0, fs[nf0])  # the sparse OR into empty slots
+    s.assign(nf0 + 1, fs[nf0 + 1])
+    assert np.array_equal(s.probe(look), oracle.probe_fixed(rs, look))
+    s.clear_slot(0)
+    s.assign(1, fs[nf - 1])  # the dense rewrite
+    exp = [oracle.OracleFilter(m), rs[nf - 1]] + rs[2:]
+    assert np.array_equal(s.probe(look), oracle.probe_fixed(exp, look))
 
 
 @pytest.mark.parametrize("m", [100003, 1 << 20, 1 << 25])

@@ -4,7 +4,7 @@ import sys
 
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])  # the line (a leg run prints only its leg)
 r = d.get("roofline")
-if r:
+if r and "random_read_roofline" in r:  # (a --workload c4 line's roofline is the build's)
     print(f"probe C3 {d['value'] / 1e12:.3f} T/s {d['ms_per_step'] * 1e3:.1f} us/step  frac {r['frac']} "
           f"one-lane {r.get('frac_one_lane')} ({r.get('kernel_avg_us_one_lane')} us)  "
           f"rr {r['random_read_roofline']['frac']}")

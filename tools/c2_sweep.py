@@ -9,7 +9,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SETTINGS = [{}, {"CB_BUILD_KPT": "2"}, {"CB_BUILD_KPT": "1"}, {"CB_BUILD_TB": "18"},
-            {"CB_BUILD_TB": "18", "CB_BUILD_KPT": "2"}, {"CB_BUILD_TILE_NT": "512", "CB_BUILD_TB": "18"}]
+            {"CB_BUILD_TB": "18", "CB_BUILD_KPT": "2"}]
 if len(sys.argv) > 1:
     SETTINGS = json.loads(sys.argv[1])
 for env in SETTINGS:

@@ -1,8 +1,11 @@
-"""bench.py on the experiment build of the library (build/exp/libcassbloom.so,
-`make -C lsmt_amd/csrc EXTRA=-DCB_EXPERIMENTS BUILD=../../build/exp/obj
-OUT=../../build/exp/libcassbloom.so`): the A/B knobs (CB_BUILD_*, CB_PROBE_*,
-CB_SET_*, CB_BIN_T, CB_ORDER_FENCE) are compiled only there. Usage: python
-tools/expbench.py [bench.py args]; set the knobs in the environment.
+"""bench.py on an experiment build of the library (build/exp/libcassbloom.so,
+`make -C lsmt_amd/csrc EXTRA="-DCB_EXPERIMENTS ..." BUILD=../../build/exp/obj
+OUT=../../build/exp/libcassbloom.so`, or the build EXPBENCH_LIB names). The
+knobs live only there, in two kinds (lsmt_amd/csrc/knobs.hpp indexes them):
+host-side planning and dispatch overrides, set in the environment of this
+run, and device-side variants, which are -D constants of the build itself
+(another value is another build). Usage: python tools/expbench.py [bench.py
+args].
 
 The loader module is installed under its package name before the package is
 imported: lsmt_amd/__init__.py loads the library at import, so setting

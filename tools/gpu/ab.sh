@@ -7,13 +7,15 @@
 # LEG: c5 | wide (bench.py --leg), c3 | c4 (bench.py --workload, the whole
 #   default line for c3), or c2_lane (build/tools/c2_lane: one-lane C2
 #   device time of the given library, tools/c2_lane.hip).
-# VARIANT = label[,lib][,ENV=value ...]. lib is an experiment build of the
-#   library, made in this container with
+# VARIANT = label[,lib][,ENV=value ...]. lib is the directory of another
+#   build of the library (an experiment build, or another commit's), made with
 #     make -C lsmt_amd/csrc EXTRA="-DCB_EXPERIMENTS ..." BUILD=../../build/x<name>/obj \
 #          OUT=../../build/x<name>/libcassbloom.so
 #   and run through tools/expbench.py; without one, the product library runs
-#   through bench.py. ENV settings apply to that variant only (the CB_* knobs
-#   of an experiment build).
+#   through bench.py. The knobs are of two kinds (lsmt_amd/csrc/knobs.hpp
+#   indexes them): device-side variants are -D constants in EXTRA, so each
+#   value is its own lib; host-side overrides are the ENV settings, which
+#   apply to that variant only and are read by experiment builds alone.
 # TESTS run first (pytest -m gpu). Output: gpurun_out/ab/<label>_<rep>.json
 # and .err, each summarised by tools/bench_brief.py as it lands.
 # Examples (HISTORY.md lists the round-5 ones):

@@ -136,22 +136,22 @@ int main(int argc, char** argv) {
   auto launch_part = [&] {  // launch_build_batch's partition
     if (p.sub)
       hipLaunchKernelGGL((k_build_part<KEY_FIXED16, MOD_POW2_32, 4, uint16_t>), dim3(p.nblk, nb), dim3(1024), lds1s, 0,
-                         bb, mp, 16u, p.T << p.sub, seg, ent, build_stores());
+                         bb, mp, 16u, p.T << p.sub, seg, ent);
     else
       hipLaunchKernelGGL((k_build_part<KEY_FIXED16, MOD_POW2_32, 4>), dim3(p.nblk, nb), dim3(1024), lds1, 0, bb, mp,
-                         p.tb, p.T, seg, ent, build_stores());
+                         p.tb, p.T, seg, ent);
   };
   const bool longruns = 2ull * p.C > 48ull * p.T;  // launch_build_batch's choice
   auto launch_tile = [&] {
     if (p.sub)
       hipLaunchKernelGGL((k_build_tile_sub<8, 2, 2, 512>), dim3(p.T, nb), dim3(512), lds2, 0, bb, p.tb, p.T, seg,
-                         p.nblk, reinterpret_cast<const uint16_t*>(ent), 2 * p.C, build_stores());
+                         p.nblk, reinterpret_cast<const uint16_t*>(ent), 2 * p.C);
     else if (longruns)
       hipLaunchKernelGGL((k_build_tile<8, 2>), dim3(p.T, nb), dim3(1024), lds2, 0, bb, p.tb, p.T, seg, p.nblk, ent,
-                         2 * p.C, build_stores());
+                         2 * p.C);
     else
       hipLaunchKernelGGL((k_build_tile<16, 1>), dim3(p.T, nb), dim3(1024), lds2, 0, bb, p.tb, p.T, seg, p.nblk, ent,
-                         2 * p.C, build_stores());
+                         2 * p.C);
   };
   allow_lds(k_build_tile<8, 2>, lds2);
   allow_lds(k_build_tile<16, 1>, lds2);
