@@ -310,6 +310,36 @@ int cb_sstable_create(const uint8_t* keys, const uint64_t* key_off, const uint8_
 int cb_sstable_create_bounded(const uint8_t* keys, const uint64_t* key_off, uint64_t key_bytes, const uint8_t* vals,
                               const uint64_t* val_off, uint64_t val_bytes, uint64_t n, uint64_t m_bits, int device,
                               void* stream, cb_table** table_out, cb_filter** bloom_out);
+/* Compaction: the newest-wins merge of nt tables into one, on the device.
+ * The reference never merges its tables (every flush pushes one more onto
+ * Database::sstables and get walks them all, src/lib.rs:128-134), so the
+ * result is defined through the two reference functions it must be
+ * indistinguishable from. With tables[0] the NEWEST (cb_get_many_*'s order)
+ * and K the keys of all their lines, the new data file is, byte for byte,
+ *   SsTable::create(entries)   (src/sstable.rs:51-87)
+ *   entries = { (k, Database::get(k)) : k in K, Database::get(k) is Some }
+ * with Database::get taken over these tables alone. So: a key present in
+ * several tables keeps the line of the newest one; a line whose value
+ * STANDARD.decode rejects is an Err the walk falls through (src/lib.rs:131,
+ * src/sstable.rs:147-149), so the kept line is the newest whose value decodes
+ * and a key whose value decodes nowhere is dropped (get returns None for it
+ * before and after); lines are `key \t text \n` sorted by key bytes, every
+ * one ending in '\n', the value text copied (for a decodable text
+ * STANDARD.encode(decode(text)) == text). *bloom_out (nullable) is
+ * BloomFilter::new(m_bits) plus an insert per kept key; the zone map is the
+ * first and last kept key (cb_table_zone); cb_meta_encode gives the `.meta`.
+ * All tables on one device; inputs still pending from cb_sstable_create are
+ * finalised first; inputs are not modified, stay valid and are the caller's to
+ * destroy — the output owns all its memory, so they may be destroyed as soon
+ * as the call returns. CB_EINVAL (nothing returned): nt == 0, a null entry,
+ * tables on different devices, an input with lines that is not well-formed
+ * (cb_table_well_formed), 2^32 or more lines in all. CB_EZEROM: m_bits == 0
+ * with bloom_out non-NULL. The returned table behaves as one made by
+ * cb_sstable_create (already finalised); a result without lines is a table of
+ * length 0 (cb_table_zone: CB_EINVAL, as for n == 0). The call waits for its
+ * own stream (the output's size depends on the data), never for the device. */
+int cb_tables_compact(const cb_table* const* tables, uint32_t nt, uint64_t m_bits, void* stream,
+                      cb_table** table_out, cb_filter** bloom_out /* nullable */);
 /* Finalise a table from cb_sstable_create*: wait for its work, take its
  * results; returns its deferred error, if any. Idempotent, thread-safe. */
 int cb_table_wait(const cb_table* t);

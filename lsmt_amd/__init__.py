@@ -25,6 +25,7 @@ from .bloom import (  # noqa: E402
     TableMeta,
     get_many,
     sstable_create,
+    compact,
     zone_bounds,
     ZoneMap,
     hits_compress,
@@ -34,5 +35,5 @@ from .bloom import (  # noqa: E402
 
 __all__ = ["BloomFilter", "BloomProto", "DeviceKeys", "FilterSet", "insert_many", "KeyBatch", "device_count", "last_path",
            "probe", "set_dense", "set_path", "unpack_hits", "zone_bounds", "ZoneMap", "TableMeta", "Table", "get_many", "sstable_create",
-           "hits_compress", "hits_expand", "hits_expand_set"]
+           "compact", "hits_compress", "hits_expand", "hits_expand_set"]
 __version__ = "0.1.0"

@@ -150,6 +150,7 @@ def load():
         "cb_table_copy": ([P, u64, u64, u8p], i32),
         "cb_sstable_create": ([u8p, P, u8p, P, u64, u64, i32, P, pp, pp, pu64, pu64], i32),
         "cb_sstable_create_bounded": ([u8p, P, u64, u8p, P, u64, u64, u64, i32, P, pp, pp], i32),
+        "cb_tables_compact": ([P, u32, u64, P, pp, pp], i32),
         "cb_table_wait": ([P], i32),
         "cb_table_zone": ([P, i32, u8p, u64, pu64], i32),
         "cb_table_rebuild": ([P, u64, P, pp, pu64, pu64], i32),

@@ -808,6 +808,31 @@ def sstable_create(entries, m: int = 1024, device: int = 0, stream=None, wait: b
     return table, bloom, zone
 
 
+def compact(tables: Sequence[Table], m: int = 1024, stream=None):
+    """Newest-wins merge of well-formed tables (tables[0] newest, as get_many
+    takes them) into one, on the device (cb_tables_compact). The reference has
+    no compaction; the result is SsTable::create (src/sstable.rs:51-87) of
+    every key of the inputs with the value Database::get (src/lib.rs:128-134)
+    returns for it over them: a key keeps its newest line whose value decodes,
+    and a key whose value decodes nowhere is dropped. Returns (Table,
+    BloomFilter of m bits, ZoneMap), as sstable_create does. The inputs are
+    not modified and may be closed as soon as the call returns."""
+    if not tables:
+        arr, dev = None, 0
+    else:
+        arr = (ctypes.c_void_p * len(tables))(*[t._h.value for t in tables])
+        dev = tables[0].device
+    th, fh = ctypes.c_void_p(), ctypes.c_void_p()
+    _raise(_L().cb_tables_compact(ctypes.cast(arr, ctypes.c_void_p) if arr is not None else None, len(tables), int(m),
+                                  _stream(stream), ctypes.byref(th), ctypes.byref(fh)))
+    table = Table._adopt(th.value, dev)
+    bloom = BloomFilter(0, device=dev, _handle=fh.value)
+    zone = ZoneMap()
+    if table.nlines:
+        zone = ZoneMap(table._zone(0), table._zone(1))
+    return table, bloom, zone
+
+
 def _to_var(b: KeyBatch) -> KeyBatch:
     keys = np.ascontiguousarray(b.keys)
     offs = (np.arange(0, b.key_len * (b.n + 1), b.key_len, dtype=np.uint64) if b.key_len

@@ -11,6 +11,7 @@
 #include <cstring>
 
 #include "capi_internal.hpp"
+#include "compact.hpp"
 
 using namespace cbx;
 
@@ -969,6 +970,187 @@ int cb_table_rebuild(const cb_table* t, uint64_t m_bits, void* stream, cb_filter
     }
   }
   *bloom_out = f.release();
+  return CB_OK;
+}
+
+// Newest-wins merge (compact.hpp). Every temporary is carved from pool blocks
+// released stream-ordered on return (error returns included: nothing the
+// enqueued work touches is freed under it). The call waits for its own stream
+// for the survivors' totals (the output is sized from them), for the
+// directory's map and at the end (the zone bounds are host results).
+int cb_tables_compact(const cb_table* const* tables, uint32_t nt, uint64_t m_bits, void* stream,
+                      cb_table** table_out, cb_filter** bloom_out) {
+  if (!table_out) return fail(CB_EINVAL, "null argument");
+  *table_out = nullptr;
+  if (bloom_out) *bloom_out = nullptr;
+  if (!nt || !tables) return fail(CB_EINVAL, "no tables");
+  for (uint32_t i = 0; i < nt; ++i)
+    if (!tables[i]) return fail(CB_EINVAL, "null table");
+  const int dev = tables[0]->device;
+  for (uint32_t i = 0; i < nt; ++i)
+    if (tables[i]->device != dev) return fail(CB_EINVAL, "tables live on different devices");
+  if (bloom_out && m_bits == 0)  // BloomFilter::insert's `% 0` (src/bloom.rs:36)
+    return fail(CB_EZEROM, "attempt to calculate the remainder with a divisor of zero");
+  hipStream_t s = (hipStream_t)stream;
+  // the sources: the non-empty tables, newest first, with their line bases
+  std::vector<cb::CompactSrc> srcs;
+  uint64_t n = 0, kbound = 0;
+  for (uint32_t i = 0; i < nt; ++i) {
+    cb_table* ti = const_cast<cb_table*>(tables[i]);
+    if (int rc = finalize_table(ti)) return rc;
+    if (!ti->nlines) continue;
+    if (!ti->fast) return fail(CB_EINVAL, "an input table is not well-formed");
+    srcs.push_back(cb::CompactSrc{ti->data, ti->rec, ti->llen, n});
+    n += ti->nlines;
+    kbound += ti->len;  // the keys' bytes are among the file's
+  }
+  if (n > 0xFFFFFFFFull) return fail(CB_EINVAL, "too many lines for one compaction");
+  int rc = cb_init(dev);
+  if (rc) return rc;
+  DeviceGuard dg(dev);
+  Workspace& ws = workspace(dev, s);  // (registers s: the pool retires blocks behind it)
+  std::unique_ptr<cb_table, int (*)(cb_table*)> t(new cb_table(), cb_table_destroy);
+  std::unique_ptr<cb_filter, int (*)(cb_filter*)> f(nullptr, cb_filter_destroy);
+  t->device = dev;
+  if (bloom_out) {
+    cb_filter* fp = nullptr;
+    if ((rc = cb_filter_create(m_bits, dev, &fp))) return rc;
+    f.reset(fp);
+  }
+  struct TempBlock {
+    int dev;
+    void* p = nullptr;
+    size_t cap = 0;
+    ~TempBlock() { pool_release(dev, p, cap); }
+  } tmp{dev}, keys{dev};
+  uint64_t cnt = 0, len = 0, kbytes = 0;
+  if (n) {
+    const uint64_t tiles = cb::compact_tiles(n);
+    // the order: the bin sort where cb_sstable_create uses it (its merge-sort
+    // fallback enqueued behind it), the merge sort otherwise
+    const uint32_t T = bin_group_target(n);
+    const bool binned = T && T <= cb::bin_sort_max_group() && n > 4096 && n <= (1ull << 24);
+    size_t at = 0;
+    auto take = [&](uint64_t bytes) {
+      const size_t o = at;
+      at += (size_t)((bytes + 15) & ~15ull);
+      return o;
+    };
+    const size_t o_src = take(srcs.size() * sizeof(cb::CompactSrc)), o_klen = take(n * 8),
+                 o_ko = take((n + 1) * 8), o_scan = take(cb::scan_tmp_words(n) * 8), o_kb = take(kbound + 16),
+                 o_side = take(n * sizeof(cb::CompactSide)), o_order = take(n * sizeof(cb::SortKey)),
+                 o_sort = take(binned ? cb::bin_sort_tmp_bytes(n, T) : cb::entry_sort_tmp_bytes(n)),
+                 o_slen = take(n * 8), o_tcnt = take(tiles * 8), o_tbytes = take(tiles * 8),
+                 o_tkeys = take(tiles * 8), o_tot = take(3 * 8), o_res = take(sizeof(cb::CreateResult));
+    if (pool_alloc(dev, at, &tmp.p, &tmp.cap) != hipSuccess) {
+      tmp.p = nullptr;
+      return fail(CB_ENOMEM, "device allocation failed for a compaction's scratch");
+    }
+    uint8_t* b = (uint8_t*)tmp.p;
+    cb::CompactSrc* dsrc = (cb::CompactSrc*)(b + o_src);
+    uint64_t* klen = (uint64_t*)(b + o_klen);
+    uint64_t* ko = (uint64_t*)(b + o_ko);
+    uint8_t* kb = b + o_kb;
+    cb::CompactSide* side = (cb::CompactSide*)(b + o_side);
+    cb::SortKey* order = (cb::SortKey*)(b + o_order);
+    uint64_t* slen = (uint64_t*)(b + o_slen);
+    uint64_t *tcnt = (uint64_t*)(b + o_tcnt), *tbytes = (uint64_t*)(b + o_tbytes), *tkeys = (uint64_t*)(b + o_tkeys);
+    uint64_t* tot = (uint64_t*)(b + o_tot);
+    const uint32_t nsrc = (uint32_t)srcs.size();
+    HIP_TRY(hipMemcpyAsync(dsrc, srcs.data(), nsrc * sizeof(cb::CompactSrc), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));  // the source is pageable
+    HIP_TRY(cb::launch_compact_klen(dsrc, nsrc, n, klen, s));
+    HIP_TRY(cb::launch_scan_u64(klen, ko, n, (uint64_t*)(b + o_scan), s));
+    // the bin sort's inputs: an unsorted batch (flags[0]) and its prefix byte masks
+    cb::CreateResult* dr = (cb::CreateResult*)(b + o_res);
+    HIP_TRY(hipMemsetAsync(dr, 0, cb::kCreateHead, s));
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)&dr->flags[0], 1, 1, s));
+    HIP_TRY(cb::launch_compact_gather(dsrc, nsrc, n, ko, kb, side, &dr->dmask[0][0], s));
+    // the stable sort by key, input index last: a key's lines leave it
+    // adjacent, newest first
+    if (binned) {
+      HIP_TRY(cb::launch_bin_sort(kb, ko, n, T, order, b + o_sort, s, nullptr, nullptr, nullptr, dr));
+      HIP_TRY(cb::launch_entry_sort(nullptr, order, (cb::SortKey*)(b + o_sort), n, kb, ko, s, nullptr, nullptr,
+                                    nullptr, &dr->flags[3]));
+    } else {
+      HIP_TRY(cb::launch_entry_sort(nullptr, order, (cb::SortKey*)(b + o_sort), n, kb, ko, s));
+    }
+    HIP_TRY(cb::launch_compact_select(order, side, kb, ko, n, slen, tcnt, tbytes, tkeys, s));
+    HIP_TRY(cb::launch_tile_scan(tcnt, tiles, tot + 0, s));
+    HIP_TRY(cb::launch_tile_scan(tbytes, tiles, tot + 1, s));
+    HIP_TRY(cb::launch_tile_scan(tkeys, tiles, tot + 2, s));
+    uint64_t h[3] = {0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(h, tot, sizeof h, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    cnt = h[0];
+    len = h[1];
+    kbytes = h[2];
+    if (cnt > n || kbytes > kbound || len > kbound + n) return fail(CB_EHIP, "compaction: inconsistent totals");
+    t->len = len;
+    if (pool_alloc(dev, len + 16, (void**)&t->data, &t->data_cap) != hipSuccess) {
+      t->data = nullptr;
+      return fail(CB_ENOMEM, "device allocation failed for an SSTable buffer");
+    }
+    HIP_TRY(hipMemsetAsync(t->data + len, 0, 16, s));
+    if (cnt) {
+      t->nlines = cnt;
+      if (pool_alloc(dev, index_bytes(cnt), (void**)&t->rec, &t->rec_cap) != hipSuccess) {
+        t->rec = nullptr;
+        return fail(CB_ENOMEM, "device allocation failed for an SSTable index");
+      }
+      carve_index(t.get());
+      const size_t kb2_bytes = (size_t)((kbytes + 16 + 15) & ~15ull);
+      if (pool_alloc(dev, kb2_bytes + (cnt + 1) * 8, &keys.p, &keys.cap) != hipSuccess) {
+        keys.p = nullptr;
+        return fail(CB_ENOMEM, "device allocation failed for a compaction's keys");
+      }
+      uint8_t* kb2 = (uint8_t*)keys.p;
+      uint64_t* ko2 = (uint64_t*)(kb2 + kb2_bytes);
+      // the file and its line index in one pass (the file is not re-read)
+      HIP_TRY(cb::launch_compact_format(order, side, slen, tcnt, tbytes, tkeys, tot, n, cnt, t->data, t->rec, t->pfx,
+                                        t->fence, t->llen, kb2, ko2, s));
+      // BloomFilter::new(m) + insert per kept key (src/sstable.rs:59-63)
+      if (f) {
+        std::lock_guard<std::mutex> lk(ws.mu);
+        if ((rc = insert_locked(ws, f.get(), kb2, ko2, 0, cnt, s))) return rc;
+      }
+      // the directory's map from the new prefixes (dr's masks are reused), and
+      // the zone map's key offsets: the first and last kept key
+      uint64_t* dmask = &dr->dmask[0][0];
+      if (t->dir) {
+        HIP_TRY(hipMemsetAsync(dmask, 0, sizeof dr->dmask, s));
+        HIP_TRY(cb::launch_pfx_masks(t->pfx, cnt, dmask, s));
+      }
+      uint64_t e[2] = {0, 0}, m[cb::kDirPos][4] = {};
+      HIP_TRY(hipMemcpyAsync(&e[0], ko2 + 1, 8, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipMemcpyAsync(&e[1], ko2 + cnt - 1, 8, hipMemcpyDeviceToHost, s));
+      if (t->dir) HIP_TRY(hipMemcpyAsync(m, dmask, sizeof m, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipStreamSynchronize(s));
+      if (e[0] > kbytes || e[1] > kbytes) return fail(CB_EHIP, "compaction: inconsistent key offsets");
+      if (t->dir) {
+        t->dmap = dmap_slot(t.get());
+        HIP_TRY(cb::launch_table_dir(t->pfx, cnt, cb::make_dirmap(m, cnt), t->dir, t->dmap, s));
+      }
+      t->zmin.resize(e[0]);
+      t->zmax.resize(kbytes - e[1]);
+      if (e[0]) HIP_TRY(hipMemcpyAsync(&t->zmin[0], kb2, e[0], hipMemcpyDeviceToHost, s));
+      if (kbytes - e[1]) HIP_TRY(hipMemcpyAsync(&t->zmax[0], kb2 + e[1], kbytes - e[1], hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipStreamSynchronize(s));
+      // strictly increasing keys, a TAB on every line: by construction
+      t->fast = !g_table_exact;
+      t->has_zone = true;
+    }
+  }
+  if (!cnt) {  // no line survives: the empty file, as cb_sstable_create's n == 0
+    if (!t->data && pool_alloc(dev, 16, (void**)&t->data, &t->data_cap) != hipSuccess) {
+      t->data = nullptr;
+      return fail(CB_ENOMEM, "device allocation failed for an SSTable buffer");
+    }
+    HIP_TRY(hipMemsetAsync(t->data, 0, 16, s));
+    HIP_TRY(hipStreamSynchronize(s));
+  }
+  if (bloom_out) *bloom_out = f.release();
+  *table_out = t.release();
   return CB_OK;
 }
 

@@ -1,0 +1,251 @@
+// compact.hip — the kernels of cb_tables_compact (compact.hpp): gather the
+// input tables' keys into one batch, (the existing stable sort orders it),
+// select each key's newest decodable line, and write the merged file.
+//
+//   k_compact_klen / k_compact_gather — one lane per input line, all tables
+//       in one launch: the line's table is found by a binary search of the
+//       sources' line bases (a few hundred entries, L2-resident), its key
+//       copied to its scanned slot of the batch and its side record written.
+//   k_compact_select — one lane per sorted record. The sort's order is strict
+//       with the input index last, so the lines of one key are adjacent,
+//       newest first. A record survives when its value decodes and no earlier
+//       record of its run does: one compare with the predecessor in the
+//       common case; only a run with spoiled values walks further back. The
+//       walk reads global memory only, so a run may cross wave, block and
+//       tile edges freely. Each block leaves three tile sums.
+//   k_compact_format — one block per tile: the survivors' offsets from the
+//       scanned tile sums and a block scan, then the block copies the tile's
+//       bytes together, aligned dwords of the output assembled from the
+//       source lines (a line is `key \t text` in its input file already, so
+//       only the '\n' is new). Each survivor also writes its entry of the
+//       line index (LineRec with vdl carried over, pfx, the fence levels,
+//       llen: the file is never re-read) and packs its key for the Bloom
+//       build and the zone bounds. The directory follows from pfx
+//       (k_pfx_masks, k_table_dir), as for a file indexed by cb_table_create.
+#include <hip/hip_runtime.h>
+
+#include "blockscan.hpp"
+#include "compact.hpp"
+#include "profile.hpp"
+#include "zone.hpp"
+
+namespace cb {
+namespace {
+
+constexpr uint32_t kNT = kCompactTile;
+
+// The source of global line g: the last one whose base is <= g.
+__device__ __forceinline__ uint32_t src_of(const CompactSrc* __restrict__ src, uint32_t nsrc, uint64_t g) {
+  uint32_t lo = 0, hi = nsrc;  // base[lo] <= g < base[hi] (base[nsrc] = n)
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (src[mid].base <= g) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+
+__global__ __launch_bounds__(kNT) void k_compact_klen(const CompactSrc* __restrict__ src, uint32_t nsrc, uint64_t n,
+                                                      uint64_t* __restrict__ klen) {
+  const uint64_t g = (uint64_t)blockIdx.x * kNT + threadIdx.x;
+  if (g >= n) return;
+  const CompactSrc t = src[src_of(src, nsrc, g)];
+  klen[g] = t.rec[g - t.base].klen;
+}
+
+__global__ __launch_bounds__(kNT) void k_compact_gather(const CompactSrc* __restrict__ src, uint32_t nsrc, uint64_t n,
+                                                        const uint64_t* __restrict__ ko, uint8_t* __restrict__ kb,
+                                                        CompactSide* __restrict__ side,
+                                                        uint64_t* __restrict__ dmask) {
+  // (whole blocks: the first kSampleBlocks of them)
+  sample_pfx_masks(n, [&](uint64_t q) {
+    const CompactSrc t = src[src_of(src, nsrc, q)];
+    return t.rec[q - t.base].pfx0;
+  }, dmask);
+  const uint64_t g = (uint64_t)blockIdx.x * kNT + threadIdx.x;
+  if (g >= n) return;
+  const CompactSrc t = src[src_of(src, nsrc, g)];
+  const uint64_t l = g - t.base;
+  const LineRec r = t.rec[l];
+  CompactSide sd;
+  sd.src = t.data + r.start;
+  sd.llen = t.llen[l];
+  sd.klen = r.klen;
+  sd.vdl = r.vdl;
+  sd.pad = 0;
+  side[g] = sd;
+  uint8_t* dst = kb + ko[g];
+  for (uint32_t j = 0; j < r.klen; ++j) dst[j] = sd.src[j];
+}
+
+// Whether two sort records name the same key (their first 16 bytes and
+// lengths from the records, the rest from the batch).
+__device__ __forceinline__ bool same_key(const SortKey& a, const SortKey& b, const uint8_t* kb, const uint64_t* ko) {
+  if (a.w0 != b.w0 || a.w1 != b.w1 || a.len != b.len) return false;
+  if (a.len <= 16) return true;
+  return bytes_cmp(kb + ko[a.idx] + 16, a.len - 16, kb + ko[b.idx] + 16, b.len - 16) == 0;
+}
+
+__global__ __launch_bounds__(kNT) void k_compact_select(const SortKey* __restrict__ order,
+                                                        const CompactSide* __restrict__ side,
+                                                        const uint8_t* __restrict__ kb,
+                                                        const uint64_t* __restrict__ ko, uint64_t n,
+                                                        uint64_t* __restrict__ slen, uint64_t* __restrict__ tcnt,
+                                                        uint64_t* __restrict__ tbytes,
+                                                        uint64_t* __restrict__ tkeys) {
+  const uint64_t p = (uint64_t)blockIdx.x * kNT + threadIdx.x;
+  uint64_t len = 0, kl = 0;
+  if (p < n) {
+    const SortKey a = order[p];
+    const CompactSide sa = side[a.idx];
+    if (sa.vdl != kBadValue) {
+      bool keep = true;
+      for (uint64_t q = p; q-- > 0;) {  // the newer lines of the same key
+        const SortKey b = order[q];
+        if (!same_key(a, b, kb, ko)) break;
+        if (side[b.idx].vdl != kBadValue) {
+          keep = false;
+          break;
+        }
+      }
+      if (keep) {
+        len = (uint64_t)sa.llen + 1;
+        kl = sa.klen;
+      }
+    }
+    slen[p] = len;
+  }
+  uint64_t tc, tl, tk;
+  (void)block_scan_sum2<(int)kNT>(len ? 1 : 0, len, kl, &tc, &tl, &tk);
+  if (threadIdx.x == 0) {
+    tcnt[blockIdx.x] = tc;
+    tbytes[blockIdx.x] = tl;
+    tkeys[blockIdx.x] = tk;
+  }
+}
+
+__global__ __launch_bounds__(kNT) void k_compact_format(const SortKey* __restrict__ order,
+                                                        const CompactSide* __restrict__ side,
+                                                        const uint64_t* __restrict__ slen,
+                                                        const uint64_t* __restrict__ tcnt,
+                                                        const uint64_t* __restrict__ tbytes,
+                                                        const uint64_t* __restrict__ tkeys,
+                                                        const uint64_t* __restrict__ totals, uint64_t n,
+                                                        uint64_t nl, uint8_t* __restrict__ out,
+                                                        LineRec* __restrict__ rec, uint64_t* __restrict__ pfx,
+                                                        uint64_t* __restrict__ fence, uint32_t* __restrict__ llen,
+                                                        uint8_t* __restrict__ kb2, uint64_t* __restrict__ ko2) {
+  __shared__ uint64_t s_off[kNT + 1];     // survivor i's first byte in the tile
+  __shared__ const uint8_t* s_src[kNT];   // its `key \t text`
+  __shared__ uint32_t s_ll[kNT];          // that many bytes, then '\n'
+  const uint64_t p = (uint64_t)blockIdx.x * kNT + threadIdx.x;
+  const uint64_t len = p < n ? slen[p] : 0;
+  CompactSide sd{};
+  if (len) sd = side[order[p].idx];
+  uint64_t tl, tc, tk;
+  const uint64_t off = block_scan<(int)kNT>(len, &tl);
+  const uint64_t ci = block_scan<(int)kNT>(len ? 1 : 0, &tc);
+  const uint64_t kof = block_scan<(int)kNT>(len ? sd.klen : 0, &tk);
+  if (blockIdx.x == 0 && threadIdx.x == 0) ko2[totals[0]] = totals[2];
+  if (!tc) return;  // (uniform)
+  if (len) {
+    s_off[ci] = off;
+    s_src[ci] = sd.src;
+    s_ll[ci] = sd.llen;
+    // the survivor's key into the packed batch
+    const uint64_t k0 = tkeys[blockIdx.x] + kof;
+    ko2[tcnt[blockIdx.x] + ci] = k0;
+    for (uint32_t j = 0; j < sd.klen; ++j) kb2[k0 + j] = sd.src[j];
+    // its index entry, as k_format writes one: line l of the new file
+    const uint64_t l = tcnt[blockIdx.x] + ci;
+    LineRec lr;
+    lr.start = tbytes[blockIdx.x] + off;
+    load16(sd.src, sd.klen, lr.pfx0, lr.pfx2);
+    lr.klen = sd.klen;
+    lr.vdl = sd.vdl;
+    rec[l] = lr;
+    pfx[l] = lr.pfx0;
+    llen[l] = sd.llen;
+    fence_put(fence, nl, l, lr.pfx0);
+  }
+  if (threadIdx.x == 0) s_off[tc] = tl;
+  __syncthreads();
+  const uint32_t nsv = (uint32_t)tc;
+  // byte j of the tile: survivor i = the last with s_off[i] <= j
+  auto line_of = [&](uint64_t j) {
+    uint32_t lo = 0, hi = nsv;
+    while (hi - lo > 1) {
+      const uint32_t mid = (lo + hi) >> 1;
+      if (s_off[mid] <= j) lo = mid;
+      else hi = mid;
+    }
+    return lo;
+  };
+  auto byte_at = [&](uint32_t i, uint64_t j) -> uint32_t {
+    const uint64_t b = j - s_off[i];
+    return b < s_ll[i] ? s_src[i][b] : (uint32_t)'\n';
+  };
+  // out[base .. base + tl): bytes up to the first 4-aligned address, then
+  // aligned dwords, then the tail
+  uint8_t* g = out + tbytes[blockIdx.x];
+  const uint64_t mis = (4 - ((uintptr_t)g & 3)) & 3;
+  const uint64_t head = mis < tl ? mis : tl;
+  if (threadIdx.x < head) g[threadIdx.x] = (uint8_t)byte_at(line_of(threadIdx.x), threadIdx.x);
+  const uint64_t body = (tl - head) / 4;
+  uint32_t* gw = reinterpret_cast<uint32_t*>(g + head);
+  for (uint64_t w = threadIdx.x; w < body; w += kNT) {
+    const uint64_t j0 = head + 4 * w;
+    uint32_t i = line_of(j0), v = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < 4; ++k) {
+      while (j0 + k >= s_off[i + 1]) ++i;  // (j0 + k < tl = s_off[nsv]: stops at a survivor)
+      v |= byte_at(i, j0 + k) << (8 * k);
+    }
+    gw[w] = v;
+  }
+  const uint64_t tail0 = head + 4 * body;
+  if (tail0 + threadIdx.x < tl) g[tail0 + threadIdx.x] = (uint8_t)byte_at(line_of(tail0 + threadIdx.x), tail0 + threadIdx.x);
+}
+
+inline uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + kNT - 1) / kNT); }
+
+}  // namespace
+
+hipError_t launch_compact_klen(const CompactSrc* src, uint32_t nsrc, uint64_t n, uint64_t* klen, hipStream_t s) {
+  if (!n) return hipSuccess;
+  ProfScope ps("k_compact_klen", s);
+  hipLaunchKernelGGL(k_compact_klen, dim3(blocks_for(n)), dim3(kNT), 0, s, src, nsrc, n, klen);
+  return hipGetLastError();
+}
+
+hipError_t launch_compact_gather(const CompactSrc* src, uint32_t nsrc, uint64_t n, const uint64_t* ko, uint8_t* kb,
+                                 CompactSide* side, uint64_t* dmask, hipStream_t s) {
+  if (!n) return hipSuccess;
+  ProfScope ps("k_compact_gather", s);
+  hipLaunchKernelGGL(k_compact_gather, dim3(blocks_for(n)), dim3(kNT), 0, s, src, nsrc, n, ko, kb, side, dmask);
+  return hipGetLastError();
+}
+
+hipError_t launch_compact_select(const SortKey* order, const CompactSide* side, const uint8_t* kb, const uint64_t* ko,
+                                 uint64_t n, uint64_t* slen, uint64_t* tcnt, uint64_t* tbytes, uint64_t* tkeys,
+                                 hipStream_t s) {
+  if (!n) return hipSuccess;
+  ProfScope ps("k_compact_select", s);
+  hipLaunchKernelGGL(k_compact_select, dim3(blocks_for(n)), dim3(kNT), 0, s, order, side, kb, ko, n, slen, tcnt,
+                     tbytes, tkeys);
+  return hipGetLastError();
+}
+
+hipError_t launch_compact_format(const SortKey* order, const CompactSide* side, const uint64_t* slen,
+                                 const uint64_t* tcnt, const uint64_t* tbytes, const uint64_t* tkeys,
+                                 const uint64_t* totals, uint64_t n, uint64_t nl, uint8_t* out, LineRec* rec,
+                                 uint64_t* pfx, uint64_t* fence, uint32_t* llen, uint8_t* kb2, uint64_t* ko2,
+                                 hipStream_t s) {
+  if (!n) return hipSuccess;
+  ProfScope ps("k_compact_format", s);
+  hipLaunchKernelGGL(k_compact_format, dim3(blocks_for(n)), dim3(kNT), 0, s, order, side, slen, tcnt, tbytes, tkeys,
+                     totals, n, nl, out, rec, pfx, fence, llen, kb2, ko2);
+  return hipGetLastError();
+}
+
+}  // namespace cb

@@ -1,0 +1,70 @@
+// compact.hpp — newest-wins merge of well-formed tables into one data file
+// (compact.hip; the C ABI's cb_tables_compact).
+//
+// The reference never merges its tables, so the result is defined through
+// the two functions it must be indistinguishable from: for tables T[0..nt),
+// T[0] newest, the file is SsTable::create (src/sstable.rs:51-87) of
+// { (k, Database::get(k)) : k a key of any line, get(k) is Some }, with
+// Database::get (src/lib.rs:128-134) taken over T alone. get keeps the first
+// Ok(Some) of the newest-first walk, so a key keeps the line of the newest
+// table whose value decodes (vdl != kBadValue), and a key whose value decodes
+// nowhere is dropped. A kept line's text is what STANDARD.encode would write
+// again, so lines are copied, never re-encoded.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "flush.hpp"
+#include "sstable.hpp"
+
+namespace cb {
+
+// One input table (non-empty, well-formed) and the number of lines before it
+// in newest-first order: global line g belongs to the last source whose base
+// is <= g.
+struct CompactSrc {
+  const uint8_t* data;
+  const LineRec* rec;
+  const uint32_t* llen;
+  uint64_t base;
+};
+
+// What the later passes need of input line g once the sort has moved its
+// record: where `key \t text` starts, its length (the line without '\n'), the
+// key's length and the value's decoded length.
+struct CompactSide {
+  const uint8_t* src;
+  uint32_t llen, klen, vdl, pad;
+};
+
+constexpr uint32_t kCompactTile = 256;  // records per select / format block
+inline uint64_t compact_tiles(uint64_t n) { return n ? (n + kCompactTile - 1) / kCompactTile : 1; }
+
+// klen[g] = the key length of global line g (the scan of these is ko).
+hipError_t launch_compact_klen(const CompactSrc* src, uint32_t nsrc, uint64_t n, uint64_t* klen, hipStream_t s);
+// The keys of all lines as one ragged batch (kb, ko) in newest-first order
+// (a smaller index is a newer line), and side[g]; dmask[kDirPos][4] |= the
+// prefix bytes of kDirSample evenly spaced lines (the bin sort's map; the
+// caller zeroes it).
+hipError_t launch_compact_gather(const CompactSrc* src, uint32_t nsrc, uint64_t n, const uint64_t* ko, uint8_t* kb,
+                                 CompactSide* side, uint64_t* dmask, hipStream_t s);
+// Over the sorted records (equal keys adjacent, newest first): slen[p] = the
+// output line's length (with its '\n') when record p is its key's newest line
+// with a decodable value, else 0; per tile of kCompactTile records the number
+// of survivors, their line bytes and their key bytes.
+hipError_t launch_compact_select(const SortKey* order, const CompactSide* side, const uint8_t* kb, const uint64_t* ko,
+                                 uint64_t n, uint64_t* slen, uint64_t* tcnt, uint64_t* tbytes, uint64_t* tkeys,
+                                 hipStream_t s);
+// From the scanned tile sums: the file (out: the survivors' lines `key \t
+// text \n` back to back), its line index without re-reading it (sstable.hpp
+// layout: survivor l is line l of nl; vdl carried over from the input's
+// index; the directory is built from pfx afterwards), and the survivors' keys
+// as a ragged batch (kb2, ko2). totals = {survivors, file bytes, key bytes}
+// (device); nl = the survivors (host: read back to size the output).
+hipError_t launch_compact_format(const SortKey* order, const CompactSide* side, const uint64_t* slen,
+                                 const uint64_t* tcnt, const uint64_t* tbytes, const uint64_t* tkeys,
+                                 const uint64_t* totals, uint64_t n, uint64_t nl, uint8_t* out, LineRec* rec,
+                                 uint64_t* pfx, uint64_t* fence, uint32_t* llen, uint8_t* kb2, uint64_t* ko2,
+                                 hipStream_t s);
+
+}  // namespace cb

@@ -110,7 +110,8 @@ hipError_t launch_entry_sort(const SortKey* in, SortKey* out, SortKey* tmp, uint
 // The same order by binning (sort.hip "bin sort"): the buckets of the
 // DirMap every launch derives from r->dmask (at most bin_sort_max_bins()) as
 // bins (monotone in the key), groups of ~T records sorted in LDS; out = the
-// sorted records, vsp / tsum as launch_entry_sort's tail. Every launch
+// sorted records, vsp / tsum as launch_entry_sort's tail (vo == nullptr:
+// neither is written). Every launch
 // returns at once when r->flags[0] is 0 (the batch is sorted). r->flags[3]
 // := 1 when the bins cannot take the batch (a single bin, or a group larger
 // than an LDS tile): out is then incomplete, and the caller enqueues

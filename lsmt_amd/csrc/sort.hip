@@ -431,8 +431,9 @@ __global__ __launch_bounds__(kBinNT) void k_bin_count(const uint8_t* __restrict_
   }
   // k_bin_sort adds the sorted line tiles into tsum (k_sorted_check left the
   // input order's there)
-  for (uint64_t i = (uint64_t)blockIdx.x * kBinNT + threadIdx.x; i < ntiles; i += (uint64_t)gridDim.x * kBinNT)
-    tsum[i] = 0;
+  if (tsum)
+    for (uint64_t i = (uint64_t)blockIdx.x * kBinNT + threadIdx.x; i < ntiles; i += (uint64_t)gridDim.x * kBinNT)
+      tsum[i] = 0;
   for (uint32_t b = threadIdx.x; b < kBins; b += kBinNT) hist[b] = 0;
   __syncthreads();
 #pragma unroll
@@ -644,29 +645,31 @@ __global__ __launch_bounds__(NT) void k_bin_sort(const SortKey* __restrict__ in,
     merge_seq(a, w, b, w, i, d - i, r, less);
   }
   // value spans, and the line lengths of this wave's outputs into the two
-  // format tiles they can touch
-  const uint64_t wbase = beg + (uint64_t)(threadIdx.x & ~63u) * kIPT;
-  const uint64_t tlo = wbase / kFormatTile;
-  uint64_t s_lo = 0, s_hi = 0;
+  // format tiles they can touch (vo == nullptr: neither, as launch_entry_sort)
+  if (vo) {
+    const uint64_t wbase = beg + (uint64_t)(threadIdx.x & ~63u) * kIPT;
+    const uint64_t tlo = wbase / kFormatTile;
+    uint64_t s_lo = 0, s_hi = 0;
 #pragma unroll
-  for (uint32_t k = 0; k < kIPT; ++k) {
-    if (t0 + k < cnt) {
-      const uint32_t i = r[k].idx;
-      const uint64_t v0 = vo[i], vl = vo[i + 1] - v0;
-      const uint64_t kl = r[k].len != 0xFFFFFFFFu ? r[k].len : less.ko[i + 1] - less.ko[i];
-      const uint64_t p = beg + t0 + k;
-      vsp[p] = make_ulonglong2(v0, vl);
-      (p / kFormatTile == tlo ? s_lo : s_hi) += line_len(kl, vl);
+    for (uint32_t k = 0; k < kIPT; ++k) {
+      if (t0 + k < cnt) {
+        const uint32_t i = r[k].idx;
+        const uint64_t v0 = vo[i], vl = vo[i + 1] - v0;
+        const uint64_t kl = r[k].len != 0xFFFFFFFFu ? r[k].len : less.ko[i + 1] - less.ko[i];
+        const uint64_t p = beg + t0 + k;
+        vsp[p] = make_ulonglong2(v0, vl);
+        (p / kFormatTile == tlo ? s_lo : s_hi) += line_len(kl, vl);
+      }
     }
-  }
 #pragma unroll
-  for (int o = 32; o; o >>= 1) {
-    s_lo += __shfl_xor(s_lo, o, 64);
-    s_hi += __shfl_xor(s_hi, o, 64);
-  }
-  if ((threadIdx.x & 63u) == 0) {
-    if (s_lo) atomicAdd((unsigned long long*)&tsum[tlo], (unsigned long long)s_lo);
-    if (s_hi) atomicAdd((unsigned long long*)&tsum[tlo + 1], (unsigned long long)s_hi);
+    for (int o = 32; o; o >>= 1) {
+      s_lo += __shfl_xor(s_lo, o, 64);
+      s_hi += __shfl_xor(s_hi, o, 64);
+    }
+    if ((threadIdx.x & 63u) == 0) {
+      if (s_lo) atomicAdd((unsigned long long*)&tsum[tlo], (unsigned long long)s_lo);
+      if (s_hi) atomicAdd((unsigned long long*)&tsum[tlo + 1], (unsigned long long)s_hi);
+    }
   }
   __syncthreads();
 #pragma unroll
