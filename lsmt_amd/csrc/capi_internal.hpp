@@ -159,11 +159,9 @@ struct TablePending {
   int device = 0;
   hipEvent_t ev = nullptr;
   cb::CreateResult* hres = nullptr;  // pinned, from the result pool
-  hipStream_t stream = nullptr;      // the creation stream (the fallback runs on it)
   const uint8_t *dk = nullptr, *dv = nullptr;
   const uint64_t *dko = nullptr, *dvo = nullptr;
   uint64_t n = 0, cap_bytes = 0;
-  bool binned = false;                // the bin sort was enqueued (its merge-sort fallback after it)
   void* staged = nullptr;             // host inputs staged into this pool block
   size_t staged_cap = 0;
 };
@@ -278,14 +276,12 @@ struct Workspace {
   uint32_t w_scr_bits = 0, w_scr_hbits = 0;
   std::vector<uint8_t> t_groups_host;
   DevBuf i_cnt, i_base, i_tmp, i_end, i_err, i_start;                 // line indexing
-  DevBuf f_vb, f_vo, f_sk, f_sk2, f_sort, f_tsum, f_flag, f_vsp;  // SsTable::create
+  DevBuf f_sk2, f_sort, f_tsum, f_flag, f_vsp;  // SsTable::create
   DevBuf x_ctl;                   // cb_hits_compress: slot / finish counters (zeroed once)
   DevBuf dense;                   // the dense set probe's entries and run table (densefs.hip)
   std::vector<std::shared_ptr<WriteMark>> marks;  // write marks, reused once no filter holds them
   cb::CompressState xst;
-  cb::CreateResult* hres = nullptr;  // pinned host mirror of f_flag (SsTable::create)
   uint64_t* htot = nullptr;          // pinned, kHostScratch B: get_many's value byte total; index_table's read-backs
-  hipEvent_t ev = nullptr;           // marks hres's first copy in the stream
 };
 
 constexpr size_t kHostScratch = 16 + sizeof(uint64_t) * cb::kDirPos * 4;  // Workspace::htot bytes

@@ -383,6 +383,100 @@ cb::DirMap* dmap_slot(const cb_table* t) {
   return t->dir ? (cb::DirMap*)((uint8_t*)t->dir + dir_bytes(t->nlines)) : nullptr;
 }
 
+// ---- the steps every maker of a table shares (cb_table_create's index_table,
+// cb_sstable_create's sstable_enqueue / finalize_locked, cb_tables_compact) ----
+
+// The file's buffer (the file and its 16 bytes of slack, or a bound on them)
+// and the index of nl lines, from the pool; a failure leaves the pointer null.
+int alloc_file(cb_table* t, uint64_t bytes) {
+  if (pool_alloc(t->device, bytes, (void**)&t->data, &t->data_cap) != hipSuccess) {
+    t->data = nullptr;
+    return fail(CB_ENOMEM, "device allocation failed for an SSTable buffer");
+  }
+  return CB_OK;
+}
+int alloc_index(cb_table* t, uint64_t nl) {
+  t->nlines = nl;
+  if (pool_alloc(t->device, index_bytes(nl), (void**)&t->rec, &t->rec_cap) != hipSuccess) {
+    t->rec = nullptr;
+    return fail(CB_ENOMEM, "device allocation failed for an SSTable index");
+  }
+  carve_index(t);
+  return CB_OK;
+}
+void drop_index(cb_table* t) {
+  pool_release(t->device, t->rec, t->rec_cap);
+  t->rec = nullptr;
+  t->pfx = t->fence = nullptr;
+  t->dir = t->llen = nullptr;
+  t->dmap = nullptr;
+  t->nlines = 0;
+}
+
+// Bin-sort group target: ~n / 1536 records (six 1024-record group sorts per
+// CU on 256 CUs, one wave), at least 640, at most 1536 (2048-record sorts).
+uint32_t bin_group_target(uint64_t n) {
+  static const int knob = cb::knob_int("CB_BIN_T", -1);  // group size target (tuning); 0 disables the bin sort
+  if (knob >= 0) return (uint32_t)knob;
+  return (uint32_t)std::min<uint64_t>(1536, std::max<uint64_t>(640, (n + 1535) / 1536));
+}
+
+// The stable sort of n keys: the bin sort for batches past one merge-sort tile
+// (its fallback, the merge sort, enqueued behind it), the merge sort alone
+// for smaller ones and past 2^24.
+struct SortPlan {
+  bool binned;
+  uint32_t T;          // the bin sort's group target
+  uint64_t tmp_bytes;  // the scratch enqueue_key_sort needs
+};
+SortPlan plan_key_sort(uint64_t n) {
+  const uint32_t T = bin_group_target(n);
+  const bool binned = T && T <= cb::bin_sort_max_group() && n > 4096 && n <= (1ull << 24);
+  return SortPlan{binned, T, binned ? cb::bin_sort_tmp_bytes(n, T) : cb::entry_sort_tmp_bytes(n)};
+}
+// order = the records of (kb, ko) in stable key order, on s. Every launch
+// returns at once unless dr->flags[0] says the batch is unsorted; the merge
+// sort behind a bin sort runs only when that set dr->flags[3] (one bin, or a
+// bin larger than an LDS tile: keys sharing a long prefix), and then rewrites
+// the records, value spans and tile sums whole. vo == nullptr: no value tail
+// (vsp and tsum are not written).
+int enqueue_key_sort(const SortPlan& plan, const uint8_t* kb, const uint64_t* ko, uint64_t n, cb::SortKey* order,
+                     void* tmp, cb::CreateResult* dr, hipStream_t s, const uint64_t* vo, ulonglong2* vsp,
+                     uint64_t* tsum) {
+  const auto& [binned, T, tmp_bytes] = plan;
+  if (binned) HIP_TRY(cb::launch_bin_sort(kb, ko, n, T, order, tmp, s, vo, vsp, tsum, dr));
+  HIP_TRY(cb::launch_entry_sort(order, (cb::SortKey*)tmp, n, kb, ko, s, vo, vsp, tsum, &dr->flags[binned ? 3 : 0]));
+  return CB_OK;
+}
+
+// The directory of a table whose prefixes are written, in two halves around
+// the caller's one copy-back and wait: the byte values of every prefix
+// position into dmask (device, kDirMaskBytes), then, from their host copy,
+// the map and the directory itself. Nothing for a table too small for one.
+constexpr size_t kDirMaskBytes = sizeof(cb::CreateResult::dmask);
+int enqueue_pfx_masks(const cb_table* t, uint64_t* dmask, hipStream_t s) {
+  if (!t->dir) return CB_OK;
+  HIP_TRY(hipMemsetAsync(dmask, 0, kDirMaskBytes, s));
+  HIP_TRY(cb::launch_pfx_masks(t->pfx, t->nlines, dmask, s));
+  return CB_OK;
+}
+int enqueue_directory(cb_table* t, const uint64_t (&masks)[cb::kDirPos][4], hipStream_t s) {
+  if (!t->dir) return CB_OK;
+  t->dmap = dmap_slot(t);
+  HIP_TRY(cb::launch_table_dir(t->pfx, t->nlines, cb::make_dirmap(masks, t->nlines), t->dir, t->dmap, s));
+  return CB_OK;
+}
+
+// An empty table's file: 16 zero bytes (allocated here unless the caller
+// has), complete on return.
+int finish_empty_file(cb_table* t, hipStream_t s) {
+  if (!t->data)
+    if (int rc = alloc_file(t, 16)) return rc;
+  HIP_TRY(hipMemsetAsync(t->data, 0, 16, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return CB_OK;
+}
+
 // Line index of t->data[0..t->len) (count -> scan -> emit -> finish -> keys).
 // Temporaries come from the stream's workspace (taken here: callers must not
 // hold its lock); the index itself is one allocation: rec | pfx | fence.
@@ -395,7 +489,7 @@ int index_table(cb_table* t, hipStream_t s) {
   HIP_TRY(ws.i_cnt.reserve(nb * 8, s));
   HIP_TRY(ws.i_base.reserve((nb + 1) * 8, s));
   HIP_TRY(ws.i_tmp.reserve(cb::scan_tmp_words(nb) * 8, s));
-  HIP_TRY(ws.i_err.reserve(16 + sizeof(uint64_t) * cb::kDirPos * 4, s));  // error words, then the prefix byte masks
+  HIP_TRY(ws.i_err.reserve(16 + kDirMaskBytes, s));  // error words, then the prefix byte masks
   uint64_t* cnt = (uint64_t*)ws.i_cnt.p;
   uint64_t* base = (uint64_t*)ws.i_base.p;
   uint32_t* err = (uint32_t*)ws.i_err.p;
@@ -405,12 +499,7 @@ int index_table(cb_table* t, hipStream_t s) {
   HIP_TRY(hipStreamSynchronize(s));
   if (!t->nlines) return CB_OK;
   const uint64_t nl = t->nlines;
-  const size_t bytes = index_bytes(nl);
-  if (pool_alloc(t->device, bytes, (void**)&t->rec, &t->rec_cap) != hipSuccess) {
-    t->rec = nullptr;
-    return fail(CB_ENOMEM, "device allocation failed for an SSTable index");
-  }
-  carve_index(t);
+  if (int rc = alloc_index(t, nl)) return rc;
   HIP_TRY(ws.i_start.reserve(nl * 8, s));
   HIP_TRY(ws.i_end.reserve(nl * 8, s));
   uint64_t* start = (uint64_t*)ws.i_start.p;
@@ -424,28 +513,19 @@ int index_table(cb_table* t, hipStream_t s) {
   // prefix + fence index, value validity and the well-formed check (sstable.hpp)
   HIP_TRY(cb::launch_line_keys(t->data, nl, t->rec, t->llen, t->pfx, t->fence, err + 1, s));
   // the byte values of every prefix position (the directory's map)
-  uint64_t* dmask = (uint64_t*)(err + 4);
-  if (t->dir) {
-    HIP_TRY(hipMemsetAsync(dmask, 0, sizeof(uint64_t) * cb::kDirPos * 4, s));
-    HIP_TRY(cb::launch_pfx_masks(t->pfx, nl, dmask, s));
-  }
+  if (int rc = enqueue_pfx_masks(t, (uint64_t*)(err + 4), s)) return rc;
   // the error words and the masks in one pinned copy, one wait
   if (!ws.htot) HIP_TRY(hipHostMalloc((void**)&ws.htot, kHostScratch, hipHostMallocDefault));
-  HIP_TRY(hipMemcpyAsync(ws.htot, err, 16 + (t->dir ? sizeof(uint64_t) * cb::kDirPos * 4 : 0),
-                         hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(ws.htot, err, 16 + (t->dir ? kDirMaskBytes : 0), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   uint32_t e[2];
   memcpy(e, ws.htot, 8);
   if (e[0]) return fail(CB_EINVAL, "an SSTable line is 4 GiB or longer");
   t->fast = e[1] != 0 && !g_table_exact;
-  if (t->dir && e[1]) {  // well-formed (sorted prefixes): the directory applies
-    uint64_t m[cb::kDirPos][4];
-    memcpy(m, ws.htot + 2, sizeof m);
-    const cb::DirMap dm = cb::make_dirmap(m, nl);
-    t->dmap = dmap_slot(t);
-    HIP_TRY(cb::launch_table_dir(t->pfx, nl, dm, t->dir, t->dmap, s));
-  }
-  return CB_OK;
+  if (!e[1]) return CB_OK;  // not well-formed: no directory (it needs sorted prefixes)
+  uint64_t m[cb::kDirPos][4];
+  memcpy(m, ws.htot + 2, sizeof m);
+  return enqueue_directory(t, m, s);
 }
 
 // ---- SsTable::create: enqueue now, finalise on first use ----
@@ -501,14 +581,6 @@ TablePending::~TablePending() {
 
 namespace {
 
-// Bin-sort group target: ~n / 1536 records (six 1024-record group sorts per
-// CU on 256 CUs, one wave), at least 640, at most 1536 (2048-record sorts).
-uint32_t bin_group_target(uint64_t n) {
-  static const int knob = cb::knob_int("CB_BIN_T", -1);  // group size target (tuning); 0 disables the bin sort
-  if (knob >= 0) return (uint32_t)knob;
-  return (uint32_t)std::min<uint64_t>(1536, std::max<uint64_t>(640, (n + 1535) / 1536));
-}
-
 // The format pass and everything after the sort, on s (ws.mu held).
 int enqueue_format(cb_table* t, Workspace& ws, const TablePending& p, cb::CreateResult* dr, hipStream_t s) {
   const uint64_t n = p.n;
@@ -540,7 +612,6 @@ int sstable_enqueue(const uint8_t* keys, const uint64_t* key_off, uint64_t kbyte
   TablePending& p = *pend;
   p.device = device;
   p.n = n;
-  p.stream = s;
   // an error return past this point may leave work enqueued that reads the
   // staged block or writes the result slot: finish the stream before `pend`
   // hands them back (declared after pend, so it runs first)
@@ -619,30 +690,21 @@ int sstable_enqueue(const uint8_t* keys, const uint64_t* key_off, uint64_t kbyte
   // the file's buffer: sum(k + 2 + 4 ceil(v / 3)) <= K + 2n + (4V + 8n) / 3,
   // plus slack; its length comes back with the results
   p.cap_bytes = kbytes + 2 * n + (4 * vbytes + 8 * n) / 3 + 1 + 16;
-  if (pool_alloc(device, p.cap_bytes, (void**)&t->data, &t->data_cap) != hipSuccess) {
-    t->data = nullptr;
-    return fail(CB_ENOMEM, "device allocation failed for an SSTable buffer");
-  }
+  if ((rc = alloc_file(t.get(), p.cap_bytes))) return rc;
   if (!n) {  // an empty file: nothing to sort, index or bound
     on_error.ok = false;
-    HIP_TRY(hipMemsetAsync(t->data, 0, 16, s));
     if (bloom_out) {
       cb_filter* fp = nullptr;
       if ((rc = cb_filter_create(m_bits, device, &fp))) return rc;
       *bloom_out = fp;
     }
     t->pend = std::move(pend);  // (no result block: the staged block is released with the table)
-    HIP_TRY(hipStreamSynchronize(s));
+    if ((rc = finish_empty_file(t.get(), s))) return rc;
     on_error.ok = true;
     *table_out = t.release();
     return CB_OK;
   }
-  t->nlines = n;
-  if (pool_alloc(device, index_bytes(n), (void**)&t->rec, &t->rec_cap) != hipSuccess) {
-    t->rec = nullptr;
-    return fail(CB_ENOMEM, "device allocation failed for an SSTable index");
-  }
-  carve_index(t.get());
+  if ((rc = alloc_index(t.get(), n))) return rc;
   ResultSlot slot;
   if ((rc = result_slot(&slot))) return rc;
   p.hres = slot.h;
@@ -667,24 +729,12 @@ int sstable_enqueue(const uint8_t* keys, const uint64_t* key_off, uint64_t kbyte
   }
   // the stable sort by key, enqueued before anyone knows whether the batch
   // needs one: every sort launch returns at once for a sorted batch (memtable
-  // flushes arrive sorted). Bin sort for 4096 < n <= 2^24 (its fallback, at
-  // finalisation, is the merge sort); the merge sort otherwise.
-  const uint32_t T = bin_group_target(n);
-  p.binned = T && T <= cb::bin_sort_max_group() && n > 4096 && n <= (1ull << 24);
-  const uint64_t tmp = p.binned ? cb::bin_sort_tmp_bytes(n, T) : cb::entry_sort_tmp_bytes(n);
-  HIP_TRY(ws.f_sort.reserve(tmp, s));
-  if (p.binned) {
-    HIP_TRY(cb::launch_bin_sort(p.dk, p.dko, n, T, (cb::SortKey*)ws.f_sk2.p, ws.f_sort.p, s, p.dvo,
-                                (ulonglong2*)ws.f_vsp.p, tsum, dr));
-    // its fallback, on the device and on this stream: the merge sort, whose
-    // launches return at once unless the bin sort set flags[3] (one bin, or a
-    // bin larger than an LDS tile: keys sharing a long prefix); it rewrites
-    // the records, value spans and tile sums whole
-    HIP_TRY(cb::launch_entry_sort(nullptr, (cb::SortKey*)ws.f_sk2.p, (cb::SortKey*)ws.f_sort.p, n, p.dk, p.dko, s,
-                                  p.dvo, (ulonglong2*)ws.f_vsp.p, tsum, &dr->flags[3]));
-  } else
-    HIP_TRY(cb::launch_entry_sort(nullptr, (cb::SortKey*)ws.f_sk2.p, (cb::SortKey*)ws.f_sort.p, n, p.dk, p.dko, s,
-                                  p.dvo, (ulonglong2*)ws.f_vsp.p, tsum, &dr->flags[0]));
+  // flushes arrive sorted)
+  const SortPlan plan = plan_key_sort(n);
+  HIP_TRY(ws.f_sort.reserve(plan.tmp_bytes, s));
+  if ((rc = enqueue_key_sort(plan, p.dk, p.dko, n, (cb::SortKey*)ws.f_sk2.p, ws.f_sort.p, dr, s, p.dvo,
+                             (ulonglong2*)ws.f_vsp.p, tsum)))
+    return rc;
   if ((rc = enqueue_format(t.get(), ws, p, dr, s))) return rc;
   HIP_TRY(hipMemcpyAsync(p.hres, dr, sizeof(cb::CreateResult), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipEventRecord(p.ev, s));
@@ -737,13 +787,7 @@ int finalize_locked(cb_table* t) {
   if (hr->flags[1]) {
     // a key holds '\n' or '\t': the file's lines are not the entries, so
     // index it the way SsTable::get splits it (src/sstable.rs:142-146)
-    pool_release(t->device, t->rec, t->rec_cap);
-    t->rec = nullptr;
-    t->pfx = t->fence = nullptr;
-    t->llen = nullptr;
-    t->dir = nullptr;
-    t->dmap = nullptr;
-    t->nlines = 0;
+    drop_index(t);
     int rc = index_table(t, nullptr);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(nullptr));
@@ -774,9 +818,6 @@ int finalize_table(cb_table* t) {
 }
 
 }  // namespace cbx
-
-namespace {
-}  // namespace
 
 extern "C" {
 
@@ -811,10 +852,7 @@ int cb_table_create(const uint8_t* data, uint64_t len, int device, void* stream,
   std::unique_ptr<cb_table, int (*)(cb_table*)> t(new cb_table(), cb_table_destroy);
   t->device = device;
   t->len = len;
-  if (pool_alloc(device, len + 16, (void**)&t->data, &t->data_cap) != hipSuccess) {
-    t->data = nullptr;
-    return fail(CB_ENOMEM, "device allocation failed for an SSTable buffer");
-  }
+  if ((rc = alloc_file(t.get(), len + 16))) return rc;
   HIP_TRY(hipMemsetAsync(t->data + len, 0, 16, s));
   if (len) HIP_TRY(hipMemcpyAsync(t->data, data, len, hipMemcpyDefault, s));
   if ((rc = index_table(t.get(), s))) return rc;
@@ -1026,10 +1064,7 @@ int cb_tables_compact(const cb_table* const* tables, uint32_t nt, uint64_t m_bit
   uint64_t cnt = 0, len = 0, kbytes = 0;
   if (n) {
     const uint64_t tiles = cb::compact_tiles(n);
-    // the order: the bin sort where cb_sstable_create uses it (its merge-sort
-    // fallback enqueued behind it), the merge sort otherwise
-    const uint32_t T = bin_group_target(n);
-    const bool binned = T && T <= cb::bin_sort_max_group() && n > 4096 && n <= (1ull << 24);
+    const SortPlan plan = plan_key_sort(n);  // the order: sorted as cb_sstable_create sorts a batch
     size_t at = 0;
     auto take = [&](uint64_t bytes) {
       const size_t o = at;
@@ -1039,7 +1074,7 @@ int cb_tables_compact(const cb_table* const* tables, uint32_t nt, uint64_t m_bit
     const size_t o_src = take(srcs.size() * sizeof(cb::CompactSrc)), o_klen = take(n * 8),
                  o_ko = take((n + 1) * 8), o_scan = take(cb::scan_tmp_words(n) * 8), o_kb = take(kbound + 16),
                  o_side = take(n * sizeof(cb::CompactSide)), o_order = take(n * sizeof(cb::SortKey)),
-                 o_sort = take(binned ? cb::bin_sort_tmp_bytes(n, T) : cb::entry_sort_tmp_bytes(n)),
+                 o_sort = take(plan.tmp_bytes),
                  o_slen = take(n * 8), o_tcnt = take(tiles * 8), o_tbytes = take(tiles * 8),
                  o_tkeys = take(tiles * 8), o_tot = take(3 * 8), o_res = take(sizeof(cb::CreateResult));
     if (pool_alloc(dev, at, &tmp.p, &tmp.cap) != hipSuccess) {
@@ -1068,13 +1103,7 @@ int cb_tables_compact(const cb_table* const* tables, uint32_t nt, uint64_t m_bit
     HIP_TRY(cb::launch_compact_gather(dsrc, nsrc, n, ko, kb, side, &dr->dmask[0][0], s));
     // the stable sort by key, input index last: a key's lines leave it
     // adjacent, newest first
-    if (binned) {
-      HIP_TRY(cb::launch_bin_sort(kb, ko, n, T, order, b + o_sort, s, nullptr, nullptr, nullptr, dr));
-      HIP_TRY(cb::launch_entry_sort(nullptr, order, (cb::SortKey*)(b + o_sort), n, kb, ko, s, nullptr, nullptr,
-                                    nullptr, &dr->flags[3]));
-    } else {
-      HIP_TRY(cb::launch_entry_sort(nullptr, order, (cb::SortKey*)(b + o_sort), n, kb, ko, s));
-    }
+    if ((rc = enqueue_key_sort(plan, kb, ko, n, order, b + o_sort, dr, s, nullptr, nullptr, nullptr))) return rc;
     HIP_TRY(cb::launch_compact_select(order, side, kb, ko, n, slen, tcnt, tbytes, tkeys, s));
     HIP_TRY(cb::launch_tile_scan(tcnt, tiles, tot + 0, s));
     HIP_TRY(cb::launch_tile_scan(tbytes, tiles, tot + 1, s));
@@ -1087,18 +1116,10 @@ int cb_tables_compact(const cb_table* const* tables, uint32_t nt, uint64_t m_bit
     kbytes = h[2];
     if (cnt > n || kbytes > kbound || len > kbound + n) return fail(CB_EHIP, "compaction: inconsistent totals");
     t->len = len;
-    if (pool_alloc(dev, len + 16, (void**)&t->data, &t->data_cap) != hipSuccess) {
-      t->data = nullptr;
-      return fail(CB_ENOMEM, "device allocation failed for an SSTable buffer");
-    }
+    if ((rc = alloc_file(t.get(), len + 16))) return rc;
     HIP_TRY(hipMemsetAsync(t->data + len, 0, 16, s));
     if (cnt) {
-      t->nlines = cnt;
-      if (pool_alloc(dev, index_bytes(cnt), (void**)&t->rec, &t->rec_cap) != hipSuccess) {
-        t->rec = nullptr;
-        return fail(CB_ENOMEM, "device allocation failed for an SSTable index");
-      }
-      carve_index(t.get());
+      if ((rc = alloc_index(t.get(), cnt))) return rc;
       const size_t kb2_bytes = (size_t)((kbytes + 16 + 15) & ~15ull);
       if (pool_alloc(dev, kb2_bytes + (cnt + 1) * 8, &keys.p, &keys.cap) != hipSuccess) {
         keys.p = nullptr;
@@ -1117,20 +1138,14 @@ int cb_tables_compact(const cb_table* const* tables, uint32_t nt, uint64_t m_bit
       // the directory's map from the new prefixes (dr's masks are reused), and
       // the zone map's key offsets: the first and last kept key
       uint64_t* dmask = &dr->dmask[0][0];
-      if (t->dir) {
-        HIP_TRY(hipMemsetAsync(dmask, 0, sizeof dr->dmask, s));
-        HIP_TRY(cb::launch_pfx_masks(t->pfx, cnt, dmask, s));
-      }
+      if ((rc = enqueue_pfx_masks(t.get(), dmask, s))) return rc;
       uint64_t e[2] = {0, 0}, m[cb::kDirPos][4] = {};
       HIP_TRY(hipMemcpyAsync(&e[0], ko2 + 1, 8, hipMemcpyDeviceToHost, s));
       HIP_TRY(hipMemcpyAsync(&e[1], ko2 + cnt - 1, 8, hipMemcpyDeviceToHost, s));
       if (t->dir) HIP_TRY(hipMemcpyAsync(m, dmask, sizeof m, hipMemcpyDeviceToHost, s));
       HIP_TRY(hipStreamSynchronize(s));
       if (e[0] > kbytes || e[1] > kbytes) return fail(CB_EHIP, "compaction: inconsistent key offsets");
-      if (t->dir) {
-        t->dmap = dmap_slot(t.get());
-        HIP_TRY(cb::launch_table_dir(t->pfx, cnt, cb::make_dirmap(m, cnt), t->dir, t->dmap, s));
-      }
+      if ((rc = enqueue_directory(t.get(), m, s))) return rc;
       t->zmin.resize(e[0]);
       t->zmax.resize(kbytes - e[1]);
       if (e[0]) HIP_TRY(hipMemcpyAsync(&t->zmin[0], kb2, e[0], hipMemcpyDeviceToHost, s));
@@ -1141,14 +1156,8 @@ int cb_tables_compact(const cb_table* const* tables, uint32_t nt, uint64_t m_bit
       t->has_zone = true;
     }
   }
-  if (!cnt) {  // no line survives: the empty file, as cb_sstable_create's n == 0
-    if (!t->data && pool_alloc(dev, 16, (void**)&t->data, &t->data_cap) != hipSuccess) {
-      t->data = nullptr;
-      return fail(CB_ENOMEM, "device allocation failed for an SSTable buffer");
-    }
-    HIP_TRY(hipMemsetAsync(t->data, 0, 16, s));
-    HIP_TRY(hipStreamSynchronize(s));
-  }
+  // no line survives: the empty file, as cb_sstable_create's n == 0
+  if (!cnt && (rc = finish_empty_file(t.get(), s))) return rc;
   if (bloom_out) *bloom_out = f.release();
   *table_out = t.release();
   return CB_OK;

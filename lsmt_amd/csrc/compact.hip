@@ -34,15 +34,21 @@ namespace {
 
 constexpr uint32_t kNT = kCompactTile;
 
-// The source of global line g: the last one whose base is <= g.
-__device__ __forceinline__ uint32_t src_of(const CompactSrc* __restrict__ src, uint32_t nsrc, uint64_t g) {
-  uint32_t lo = 0, hi = nsrc;  // base[lo] <= g < base[hi] (base[nsrc] = n)
+// The last i in [0, n) with at(i) <= x (at is non-decreasing, at(0) <= x).
+template <class At>
+__device__ __forceinline__ uint32_t last_le(uint32_t n, uint64_t x, At at) {
+  uint32_t lo = 0, hi = n;  // at(lo) <= x < at(hi) (at(n) = past every x)
   while (hi - lo > 1) {
     const uint32_t mid = (lo + hi) >> 1;
-    if (src[mid].base <= g) lo = mid;
+    if (at(mid) <= x) lo = mid;
     else hi = mid;
   }
   return lo;
+}
+
+// The source of global line g: the last one whose base is <= g.
+__device__ __forceinline__ uint32_t src_of(const CompactSrc* __restrict__ src, uint32_t nsrc, uint64_t g) {
+  return last_le(nsrc, g, [&](uint32_t i) { return src[i].base; });
 }
 
 __global__ __launch_bounds__(kNT) void k_compact_klen(const CompactSrc* __restrict__ src, uint32_t nsrc, uint64_t n,
@@ -156,31 +162,17 @@ __global__ __launch_bounds__(kNT) void k_compact_format(const SortKey* __restric
     const uint64_t k0 = tkeys[blockIdx.x] + kof;
     ko2[tcnt[blockIdx.x] + ci] = k0;
     for (uint32_t j = 0; j < sd.klen; ++j) kb2[k0 + j] = sd.src[j];
-    // its index entry, as k_format writes one: line l of the new file
-    const uint64_t l = tcnt[blockIdx.x] + ci;
-    LineRec lr;
-    lr.start = tbytes[blockIdx.x] + off;
-    load16(sd.src, sd.klen, lr.pfx0, lr.pfx2);
-    lr.klen = sd.klen;
-    lr.vdl = sd.vdl;
-    rec[l] = lr;
-    pfx[l] = lr.pfx0;
-    llen[l] = sd.llen;
-    fence_put(fence, nl, l, lr.pfx0);
+    // its index entry (line tcnt + ci of the new file), by k_format's writer
+    uint64_t w0, w1;
+    load16(sd.src, sd.klen, w0, w1);
+    put_index_entry(rec, pfx, llen, fence, nl, tcnt[blockIdx.x] + ci, tbytes[blockIdx.x] + off, w0, w1, sd.klen,
+                    sd.vdl, sd.llen);
   }
   if (threadIdx.x == 0) s_off[tc] = tl;
   __syncthreads();
   const uint32_t nsv = (uint32_t)tc;
   // byte j of the tile: survivor i = the last with s_off[i] <= j
-  auto line_of = [&](uint64_t j) {
-    uint32_t lo = 0, hi = nsv;
-    while (hi - lo > 1) {
-      const uint32_t mid = (lo + hi) >> 1;
-      if (s_off[mid] <= j) lo = mid;
-      else hi = mid;
-    }
-    return lo;
-  };
+  auto line_of = [&](uint64_t j) { return last_le(nsv, j, [&](uint32_t i) { return s_off[i]; }); };
   auto byte_at = [&](uint32_t i, uint64_t j) -> uint32_t {
     const uint64_t b = j - s_off[i];
     return b < s_ll[i] ? s_src[i][b] : (uint32_t)'\n';

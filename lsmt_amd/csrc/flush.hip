@@ -5,12 +5,12 @@
 // `key \t STANDARD.encode(value) \n`. Memtable flushes arrive sorted already
 // (the memtable is a BTreeMap, src/memtable.rs:6-8), so a sortedness check
 // runs first and the sort is skipped when it passes. Otherwise entries are
-// sorted by rocPRIM's stable merge sort on 24-byte records (16-byte key
-// prefix + length + index) with a full compare only for prefix ties. Line
+// sorted by the hand-written stable sort of sort.hip (a bin sort, or an LDS
+// merge sort) on 24-byte records (16-byte key prefix + length + index) with
+// a full compare only for prefix ties. Line
 // lengths are known up front (key + 1 + 4*ceil(value/3) + 1), so an
 // exclusive scan gives every line's offset and one lane formats each line.
 #include <hip/hip_runtime.h>
-
 
 #include "blockscan.hpp"
 #include "flush.hpp"
@@ -23,7 +23,6 @@ namespace {
 constexpr uint32_t kNT = 256;  // = kFormatTile
 
 inline uint32_t blocks_for(uint64_t n, uint32_t per) { return (uint32_t)((n + per - 1) / per); }
-
 
 // The first 16 bytes of key p (output order) as zero-padded big-endian words,
 // and its length. Unsorted input: the sort record already holds them; sorted
@@ -53,15 +52,6 @@ __device__ __forceinline__ bool has_byte(uint64_t w, uint64_t m, uint32_t c) {
   return ((x - 0x0101010101010101ull) & ~x & 0x8080808080808080ull) != 0;
 }
 
-// Sort records in input order (the key's first 16 bytes read as words).
-__global__ __launch_bounds__(kNT) void k_sort_keys(const uint8_t* __restrict__ kb,
-                                                   const uint64_t* __restrict__ ko, uint64_t n,
-                                                   SortKey* __restrict__ out) {
-  const uint64_t p = (uint64_t)blockIdx.x * kNT + threadIdx.x;
-  if (p >= n) return;
-  out[p] = sort_record(kb, ko, p);
-}
-
 // Rust str order of keys q and p (q, p index the key batch) given their first
 // 16 bytes as words: from the words alone when both fit in 16 bytes.
 __device__ __forceinline__ int key_cmp(const uint8_t* kb, const uint64_t* ko, uint64_t q,
@@ -75,27 +65,14 @@ __device__ __forceinline__ int key_cmp(const uint8_t* kb, const uint64_t* ko, ui
   return bytes_cmp(kb + ko[q], ql, kb + ko[p], pl);
 }
 
-
-// The sum of each kFormatTile-line tile's lengths (order == nullptr: input
-// order), for k_format's offsets. Call uniformly.
-__device__ __forceinline__ void tile_sum(const SortKey* order, const uint64_t* ko, const uint64_t* vo,
-                                         uint64_t n, uint64_t* tsum) {
+// The sum of each kFormatTile-line tile's lengths in input order, for
+// k_format's offsets. Call uniformly.
+__device__ __forceinline__ void tile_sum(const uint64_t* ko, const uint64_t* vo, uint64_t n, uint64_t* tsum) {
   const uint64_t p = (uint64_t)blockIdx.x * kNT + threadIdx.x;
-  uint64_t len = 0;
-  if (p < n) {
-    const uint64_t i = order ? order[p].idx : p;
-    len = line_len(ko[i + 1] - ko[i], vo[i + 1] - vo[i]);
-  }
+  const uint64_t len = p < n ? line_len(ko[p + 1] - ko[p], vo[p + 1] - vo[p]) : 0;
   uint64_t total;
   (void)block_scan<kNT>(len, &total);
   if (threadIdx.x == 0) tsum[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(kNT) void k_line_sums(const SortKey* __restrict__ order,
-                                                   const uint64_t* __restrict__ ko,
-                                                   const uint64_t* __restrict__ vo, uint64_t n,
-                                                   uint64_t* __restrict__ tsum) {
-  tile_sum(order, ko, vo, n, tsum);
 }
 
 static_assert(offsetof(CreateResult, len) == kCreateHead, "the zeroed head of CreateResult");
@@ -109,7 +86,7 @@ __global__ __launch_bounds__(kNT) void k_sorted_check(const uint8_t* __restrict_
                                                       uint64_t kmax, uint64_t vmax) {
   const uint64_t p = (uint64_t)blockIdx.x * kNT + threadIdx.x;
   const uint32_t lane = threadIdx.x & 63u;
-  tile_sum(nullptr, ko, vo, n, tsum);  // the line tiles if the input is already sorted
+  tile_sum(ko, vo, n, tsum);  // the line tiles if the input is already sorted
   if (p == 0) {
     const uint64_t kt = ko[n], vt = vo[n];
     r->ktot = kt;
@@ -135,8 +112,6 @@ __global__ __launch_bounds__(kNT) void k_sorted_check(const uint8_t* __restrict_
   // returning load and an atomic per block on one word
   if (__syncthreads_or(bad) && threadIdx.x == 0) r->flags[0] = 1u;
 }
-
-
 
 // One bound of the ZoneMap (the file's first or last key, w = 0 / 1) into r:
 // input index, full length and up to kZoneInline bytes. Whole block.
@@ -249,8 +224,8 @@ __device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
 // SsTable::create's file and everything derived from it, one lane per entry p
 // (= line p; entries in key order):
 // - the line `key \t base64(value) \n` at its offset: the tile sums before
-//   the block (tsum from k_sorted_check or k_line_sums, scanned by
-//   k_tile_scan) plus the scan of the block's line lengths: no full-length
+//   the block (tsum from k_sorted_check or the sort's last launch, scanned
+//   by k_tile_scan) plus the scan of the block's line lengths: no full-length
 //   scan pass. A block's 256 lines are one
 //   contiguous range; when it fits in LDS the lanes format into LDS (staged at
 //   the range's address mod 4, so LDS and global dwords line up) and the block
@@ -345,24 +320,8 @@ __global__ __launch_bounds__(kNT) void k_format(const SortKey* __restrict__ orde
       for (uint64_t j = 0; j < kl; ++j) special |= (k[j] == '\n') | (k[j] == '\t');
     }
     special |= llen >= kNoSep;  // the re-index reports it
-    LineRec lr;
-    lr.start = o;
-    lr.pfx2 = w1;  // bytes 8..15 (zero when kl <= 8)
-    lr.klen = (uint32_t)kl;
-    lr.vdl = (uint32_t)vl;  // canonical STANDARD encoding: always decodes
-    lr.pfx0 = w0;
-    // the index and the file are written once and read by later launches
-    // (the read path): non-temporal, no L2 lines to write back at the
-    // kernel's end (k_format 52.3 -> 49.2 us after the bin sort)
-    typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-    const u32x4_t ra = {(uint32_t)lr.start, (uint32_t)(lr.start >> 32), (uint32_t)lr.pfx2,
-                        (uint32_t)(lr.pfx2 >> 32)};
-    const u32x4_t rb = {lr.klen, lr.vdl, (uint32_t)lr.pfx0, (uint32_t)(lr.pfx0 >> 32)};
-    __builtin_nontemporal_store(ra, reinterpret_cast<u32x4_t*>(rec + p));
-    __builtin_nontemporal_store(rb, reinterpret_cast<u32x4_t*>(rec + p) + 1);
-    __builtin_nontemporal_store(w0, pfx + p);
-    __builtin_nontemporal_store((uint32_t)llen, llen_out + p);
-    fence_put(fence, n, p, w0);
+    // (vdl = vl: the canonical STANDARD encoding always decodes)
+    put_index_entry(rec, pfx, llen_out, fence, n, p, o, w0, w1, (uint32_t)kl, (uint32_t)vl, (uint32_t)llen);
     if (p > 0) not_inc = key_cmp(kb, ko, pi, pkl, pw0, pw1, i, kl, w0, w1) >= 0;
   }
   // plain stores of one value from every block that has one (no atomics)
@@ -435,15 +394,6 @@ __global__ __launch_bounds__(kNT) void k_format(const SortKey* __restrict__ orde
 
 }  // namespace
 
-hipError_t launch_sort_keys(const uint8_t* kb, const uint64_t* ko, uint64_t n, SortKey* out,
-                            hipStream_t s) {
-  if (!n) return hipSuccess;
-  ProfScope ps("k_sort_keys", s);
-  hipLaunchKernelGGL(k_sort_keys, dim3(blocks_for(n, kNT)), dim3(kNT), 0, s, kb, ko, n, out);
-  return hipGetLastError();
-}
-
-
 hipError_t launch_sorted_check(const uint8_t* kb, const uint64_t* ko, const uint64_t* vo, uint64_t n,
                                CreateResult* r, uint64_t* tsum, uint64_t kmax, uint64_t vmax, hipStream_t s) {
   ProfScope ps("k_sorted_check", s);
@@ -451,17 +401,6 @@ hipError_t launch_sorted_check(const uint8_t* kb, const uint64_t* ko, const uint
                      tsum, kmax, vmax);
   return hipGetLastError();
 }
-
-hipError_t launch_line_sums(const SortKey* order, const uint64_t* ko, const uint64_t* vo, uint64_t n,
-                            uint64_t* tsum, hipStream_t s) {
-  if (!n) return hipSuccess;
-  ProfScope ps("k_line_sums", s);
-  hipLaunchKernelGGL(k_line_sums, dim3(blocks_for(n, kNT)), dim3(kNT), 0, s, order, ko, vo, n, tsum);
-  return hipGetLastError();
-}
-
-
-
 
 hipError_t launch_format(const SortKey* order, const uint8_t* kb, const uint64_t* ko,
                          const uint8_t* vb, const uint64_t* vo, const uint64_t* tsum, uint64_t n,

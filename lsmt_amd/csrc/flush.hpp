@@ -44,6 +44,29 @@ __device__ __forceinline__ void load16(const uint8_t* src, uint64_t len, uint64_
   w1 = m >= 16 ? b1 : (m > 8 ? b1 & ~(~0ull >> (8 * (m - 8))) : 0);
 }
 
+// Line l's entry of a table's index (sstable.hpp layout: LineRec, pfx, llen
+// and the fence levels), nl lines in all; w0 / w1 are the key's first 16
+// bytes as load16 gives them, llen the line's length without the '\n'. The
+// one writer for SsTable::create's format pass and for compaction's. The
+// index is written once and read by later launches (the read path):
+// non-temporal, no L2 lines to write back at the kernel's end (k_format 52.3
+// -> 49.2 us after the bin sort).
+__device__ __forceinline__ void put_index_entry(LineRec* rec, uint64_t* pfx, uint32_t* llen_out, uint64_t* fence,
+                                                uint64_t nl, uint64_t l, uint64_t start, uint64_t w0, uint64_t w1,
+                                                uint32_t klen, uint32_t vdl, uint32_t llen) {
+  static_assert(offsetof(LineRec, start) == 0 && offsetof(LineRec, pfx2) == 8 && offsetof(LineRec, klen) == 16 &&
+                    offsetof(LineRec, vdl) == 20 && offsetof(LineRec, pfx0) == 24 && sizeof(LineRec) == 32,
+                "the two 16-byte halves below are LineRec's layout");
+  typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+  const u32x4_t ra = {(uint32_t)start, (uint32_t)(start >> 32), (uint32_t)w1, (uint32_t)(w1 >> 32)};
+  const u32x4_t rb = {klen, vdl, (uint32_t)w0, (uint32_t)(w0 >> 32)};
+  __builtin_nontemporal_store(ra, reinterpret_cast<u32x4_t*>(rec + l));
+  __builtin_nontemporal_store(rb, reinterpret_cast<u32x4_t*>(rec + l) + 1);
+  __builtin_nontemporal_store(w0, pfx + l);
+  __builtin_nontemporal_store(llen, llen_out + l);
+  fence_put(fence, nl, l, w0);
+}
+
 // The sort record of entry p of a key batch (kb, ko).
 __device__ __forceinline__ SortKey sort_record(const uint8_t* kb, const uint64_t* ko, uint64_t p) {
   const uint64_t o0 = ko[p], kl = ko[p + 1] - o0;
@@ -76,9 +99,6 @@ struct CreateResult {
   uint8_t zkey[2][kZoneInline];
 };
 
-// out[i] = the sort record of key i.
-hipError_t launch_sort_keys(const uint8_t* kb, const uint64_t* ko, uint64_t n, SortKey* out,
-                            hipStream_t s);
 // Lines per tile of the file's offsets: tsum holds format_tiles(n) (>= 1)
 // sums of line lengths.
 constexpr uint32_t kFormatTile = 256;
@@ -91,20 +111,17 @@ inline uint64_t format_tiles(uint64_t n) { return n ? (n + kFormatTile - 1) / kF
 constexpr size_t kCreateHead = 32 + 16 + kDirPos * 4 * 8;  // flags, totals, dmask: zeroed per create
 hipError_t launch_sorted_check(const uint8_t* kb, const uint64_t* ko, const uint64_t* vo, uint64_t n,
                                CreateResult* r, uint64_t* tsum, uint64_t kmax, uint64_t vmax, hipStream_t s);
-// tsum = the line tiles in the order of the sort records.
-hipError_t launch_line_sums(const SortKey* order, const uint64_t* ko, const uint64_t* vo, uint64_t n,
-                            uint64_t* tsum, hipStream_t s);
 // Stable sort of the records by key, hand-written (sort.hip): LDS block
 // sorts of 4096 records, then merge-path rounds. tmp: entry_sort_tmp_bytes(n)
-// of scratch; in must not alias out or tmp. in == nullptr: the block sort
-// builds the records from the key batch itself (no launch_sort_keys pass).
+// of scratch; out must not alias tmp. The block sort builds the records from
+// the key batch (kb, ko) itself.
 // vo != nullptr: the last launch also writes, for every output p, vsp[p] =
-// {vo[idx], value length} and tsum = the line tiles in sorted order (what
-// launch_line_sums would), from the records it holds in registers.
+// {vo[idx], value length} and tsum = the line tiles in sorted order, from the
+// records it holds in registers.
 // run_if (nullable, device): every launch returns at once unless *run_if !=
 // 0 (SsTable::create enqueues the sort before it knows the batch's order).
 uint64_t entry_sort_tmp_bytes(uint64_t n);
-hipError_t launch_entry_sort(const SortKey* in, SortKey* out, SortKey* tmp, uint64_t n, const uint8_t* kb,
+hipError_t launch_entry_sort(SortKey* out, SortKey* tmp, uint64_t n, const uint8_t* kb,
                              const uint64_t* ko, hipStream_t s, const uint64_t* vo = nullptr,
                              ulonglong2* vsp = nullptr, uint64_t* tsum = nullptr, const uint32_t* run_if = nullptr);
 // The same order by binning (sort.hip "bin sort"): the buckets of the

@@ -218,19 +218,16 @@ __device__ __forceinline__ void cas(SortKey& x, SortKey& y, const RecLess& less)
   }
 }
 
-__global__ __launch_bounds__(kST) void k_sort_block(const SortKey* __restrict__ in, SortKey* __restrict__ out,
-                                                    uint64_t n, RecLess less, SortTail tl,
+__global__ __launch_bounds__(kST) void k_sort_block(SortKey* __restrict__ out, uint64_t n, RecLess less, SortTail tl,
                                                     const uint32_t* __restrict__ run_if) {
   if (run_if && !*run_if) return;  // (uniform) the batch needs no sort
   __shared__ uint64_t lds[3 * kPadded];
   const LdsTile tile{lds};
   const uint64_t base = (uint64_t)blockIdx.x * kTile;
   const uint32_t cnt = (uint32_t)(n - base < kTile ? n - base : kTile);
-  if (in) {
-    tile_load(in + base, cnt, tile);
-  } else {  // the records straight from the key batch
-    for (uint32_t i = threadIdx.x; i < kTile; i += kST) tile.set(i, i < cnt ? sort_record(less.kb, less.ko, base + i) : sentinel());
-  }
+  // the records straight from the key batch
+  for (uint32_t i = threadIdx.x; i < kTile; i += kST)
+    tile.set(i, i < cnt ? sort_record(less.kb, less.ko, base + i) : sentinel());
   __syncthreads();
   SortKey r[kIPT];
   const uint32_t t0 = threadIdx.x * kIPT;
@@ -724,7 +721,7 @@ hipError_t launch_bin_sort(const uint8_t* kb, const uint64_t* ko, uint64_t n, ui
   return hipGetLastError();
 }
 
-hipError_t launch_entry_sort(const SortKey* in, SortKey* out, SortKey* tmp, uint64_t n, const uint8_t* kb,
+hipError_t launch_entry_sort(SortKey* out, SortKey* tmp, uint64_t n, const uint8_t* kb,
                              const uint64_t* ko, hipStream_t s, const uint64_t* vo, ulonglong2* vsp,
                              uint64_t* tsum, const uint32_t* run_if) {
   if (!n) return hipSuccess;
@@ -736,7 +733,7 @@ hipError_t launch_entry_sort(const SortKey* in, SortKey* out, SortKey* tmp, uint
   const RecLess less{kb, ko};
   ProfScope ps("k_entry_sort", s);
   const SortTail none{nullptr, nullptr, nullptr}, tail{vo, vsp, tsum};
-  hipLaunchKernelGGL(k_sort_block, dim3((uint32_t)tiles), dim3(kST), 0, s, in, bufs[rounds & 1], n, less,
+  hipLaunchKernelGGL(k_sort_block, dim3((uint32_t)tiles), dim3(kST), 0, s, bufs[rounds & 1], n, less,
                      rounds ? none : tail, run_if);
   for (uint32_t r = 0; r < rounds; ++r) {
     const uint64_t w = (uint64_t)kTile << r;
