@@ -429,6 +429,53 @@ int cb_set_get_many_var(const cb_filterset* set, const cb_table* const* tables, 
                         int32_t* which, uint64_t* val_off, uint8_t* vals, uint64_t cap, uint64_t* total,
                         void* stream);
 
+/* ---- tiered filter sets: one gate and one fused get over mixed filter sizes ----
+ * A FilterSet holds filters of one size m, which fits a store whose every
+ * table is a 1024-entry flush behind BloomFilter::new(1024)
+ * (src/sstable.rs:44,59). After cb_tables_compact a store also holds one or a
+ * few large tables whose filter must be large to mean anything (110 808 keys
+ * in 1024 bits is a saturated filter; cb_tables_compact takes m_bits for that
+ * reason), in front of which sit the fresh small tables: mixed m is then the
+ * normal case. These entries take an ordered table list (tables[0] the
+ * newest) whose filters live in several FilterSets of different m, the
+ * "tiers": table t's Bloom filter and zone map are slot slots[t] of
+ * sets[tiers[t]]. The key is hashed once for all tiers.
+ *
+ * Gate: bit (key, t) is exactly what cb_set_probe_gated_* on sets[tiers[t]]
+ * reports for slot slots[t] — zone_map.contains(key) && bloom.may_contain(key)
+ * (src/sstable.rs:138) with that tier's m; gated == 0: may_contain alone.
+ * hits is [nt][ceil(n/64)] uint64, row t = table t (table order, not slot
+ * order), tail bits zero; host or device memory as for cb_set_probe_* (host
+ * buffers are staged and the call synchronises). n == 0 writes nothing.
+ *
+ * Get: Database::get's newest-first walk (src/lib.rs:128-134) over those
+ * gate bits in one launch, bit-identical in which / val_off / vals / *total
+ * to cb_get_many_* fed the gate rows above; cb_set_get_many_*'s contract,
+ * total = NULL (enqueue only, everything on the device) and the first-use
+ * build of a table's key buckets included.
+ *
+ * Limits: 1 <= ns <= 8 sets of width 32 or 64 (no wide set), 1 <= nt <= 64,
+ * tiers and slots non-NULL with tiers[t] < ns and slots[t] < that set's width,
+ * all sets and tables on one device; anything else is CB_EINVAL with nothing
+ * enqueued. A slot at or past a set's `used` reads as an empty filter (gate
+ * bit 0); a set no table names is not read; a (tier, slot) pair may repeat.
+ * A later cb_set_zone on any tier whose zone table the launch reads waits for
+ * the launch, as after cb_set_get_many_*. */
+int cb_tiers_probe_fixed(const cb_filterset* const* sets, uint32_t ns, const uint32_t* tiers,
+                         const uint32_t* slots, uint32_t nt, const uint8_t* keys, uint32_t key_len,
+                         uint64_t n, int gated, uint64_t* hits, void* stream);
+int cb_tiers_probe_var(const cb_filterset* const* sets, uint32_t ns, const uint32_t* tiers,
+                       const uint32_t* slots, uint32_t nt, const uint8_t* bytes, const uint64_t* offsets,
+                       uint64_t n, int gated, uint64_t* hits, void* stream);
+int cb_tiers_get_many_fixed(const cb_filterset* const* sets, uint32_t ns, const cb_table* const* tables,
+                            uint32_t nt, const uint32_t* tiers, const uint32_t* slots,
+                            const uint8_t* keys, uint32_t key_len, uint64_t n, int32_t* which,
+                            uint64_t* val_off, uint8_t* vals, uint64_t cap, uint64_t* total, void* stream);
+int cb_tiers_get_many_var(const cb_filterset* const* sets, uint32_t ns, const cb_table* const* tables,
+                          uint32_t nt, const uint32_t* tiers, const uint32_t* slots, const uint8_t* bytes,
+                          const uint64_t* offsets, uint64_t n, int32_t* which, uint64_t* val_off,
+                          uint8_t* vals, uint64_t cap, uint64_t* total, void* stream);
+
 /* ---- multi-GPU exchange ----
  * Each rank holds hit rows [rows][words] (uint64) for its filter subset; the
  * ranks all-gather them so every rank has the [total_rows][words] map that

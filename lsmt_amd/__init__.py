@@ -24,6 +24,8 @@ from .bloom import (  # noqa: E402
     Table,
     TableMeta,
     get_many,
+    get_many_tiers,
+    probe_tiers,
     sstable_create,
     compact,
     zone_bounds,
@@ -35,5 +37,5 @@ from .bloom import (  # noqa: E402
 
 __all__ = ["BloomFilter", "BloomProto", "DeviceKeys", "FilterSet", "insert_many", "KeyBatch", "device_count", "last_path",
            "probe", "set_dense", "set_path", "unpack_hits", "zone_bounds", "ZoneMap", "TableMeta", "Table", "get_many", "sstable_create",
-           "compact", "hits_compress", "hits_expand", "hits_expand_set"]
+           "compact", "probe_tiers", "get_many_tiers", "hits_compress", "hits_expand", "hits_expand_set"]
 __version__ = "0.1.0"

@@ -166,6 +166,10 @@ def load():
         "cb_set_get_many_var": ([P, P, u32, P, u8p, P, u64, P, P, P, u64, pu64, P], i32),
         "cb_set_probe_gated_fixed": ([P, u8p, u32, u64, P, P], i32),
         "cb_set_probe_gated_var": ([P, u8p, P, u64, P, P], i32),
+        "cb_tiers_probe_fixed": ([P, u32, P, P, u32, u8p, u32, u64, i32, P, P], i32),
+        "cb_tiers_probe_var": ([P, u32, P, P, u32, u8p, P, u64, i32, P, P], i32),
+        "cb_tiers_get_many_fixed": ([P, u32, P, u32, P, P, u8p, u32, u64, P, P, P, u64, pu64, P], i32),
+        "cb_tiers_get_many_var": ([P, u32, P, u32, P, P, u8p, P, u64, P, P, P, u64, pu64, P], i32),
         "cb_profile_enable": ([i32], i32),
         "cb_profile_reset": ([], i32),
         "cb_profile_read": ([ctypes.c_char_p, ctypes.POINTER(ctypes.c_double), pu64], i32),

@@ -887,20 +887,30 @@ def get_many(tables: Sequence[Table], keys, hits=None, hit_rows=None, stream=Non
     in one launch)."""
     if filterset is not None and hits is not None:
         raise ValueError("filterset= computes the gate itself: pass hits=None")
-    b = as_batch(keys)
     nt = len(tables)
-    arr = _table_array(tables)
+    arr = ctypes.cast(_table_array(tables), ctypes.c_void_p)
     hp, hk = _ptr_of(hits) if hits is not None else (None, None)
     rows = None
     if hit_rows is not None:
         rows = np.ascontiguousarray(hit_rows, dtype=np.uint32)
     rp = rows.ctypes.data if rows is not None else None
+    L = _L()
+    if filterset is not None:
+        return _get_many_run(L.cb_set_get_many_fixed, L.cb_set_get_many_var, (filterset._h, arr, nt, rp),
+                             keys, stream, out, wait)
+    return _get_many_run(L.cb_get_many_fixed, L.cb_get_many_var, (arr, nt, hp, rp), keys, stream, out, wait)
+
+
+def _get_many_run(fixed_fn, var_fn, head, keys, stream, out, wait):
+    """The cb_*get_many_* families share their argument tail (keys, n, which,
+    val_off, vals, cap, total, stream) and their return forms (get_many's
+    docstring); head holds the arguments before the keys."""
+    b = as_batch(keys)
     total = ctypes.c_uint64()
     if not wait and out is None:
         raise ValueError("wait=False needs out= device buffers")
     tref = ctypes.byref(total) if wait else None
     s = _stream(stream)
-    L = _L()
     if out is not None:
         which, voff, vals = out
         cap = int(vals.numel()) if hasattr(vals, "numel") else int(vals.nbytes)
@@ -914,22 +924,12 @@ def get_many(tables: Sequence[Table], keys, hits=None, hit_rows=None, stream=Non
         offp, k2 = _ptr_of(b.offsets)
 
         def call(vp, cap):
-            if filterset is not None:
-                _raise(L.cb_set_get_many_var(filterset._h, ctypes.cast(arr, ctypes.c_void_p), nt, rp, dp, offp, b.n,
-                                             wp, vo, vp, cap, tref, s))
-            else:
-                _raise(L.cb_get_many_var(ctypes.cast(arr, ctypes.c_void_p), nt, hp, rp, dp, offp, b.n,
-                                         wp, vo, vp, cap, tref, s))
+            _raise(var_fn(*head, dp, offp, b.n, wp, vo, vp, cap, tref, s))
     else:
         kp, k1 = _ptr_of(b.keys)
 
         def call(vp, cap):
-            if filterset is not None:
-                _raise(L.cb_set_get_many_fixed(filterset._h, ctypes.cast(arr, ctypes.c_void_p), nt, rp, kp, b.key_len,
-                                               b.n, wp, vo, vp, cap, tref, s))
-            else:
-                _raise(L.cb_get_many_fixed(ctypes.cast(arr, ctypes.c_void_p), nt, hp, rp, kp, b.key_len, b.n,
-                                           wp, vo, vp, cap, tref, s))
+            _raise(fixed_fn(*head, kp, b.key_len, b.n, wp, vo, vp, cap, tref, s))
     if out is not None:
         call(_ptr_of(vals)[0], cap)
         return which, voff, (int(total.value) if wait else None)
@@ -937,6 +937,65 @@ def get_many(tables: Sequence[Table], keys, hits=None, hit_rows=None, stream=Non
     vals = np.zeros(max(int(total.value), 1), np.uint8)
     call(vals.ctypes.data, int(total.value))
     return which[: b.n], voff, vals[: int(total.value)].tobytes()
+
+
+def _tier_args(sets: Sequence[FilterSet], tiers, slots):
+    """(set handle array, ns, tiers uint32[nt], slots uint32[nt]) of a tiered call."""
+    hs = [st._h.value for st in sets]
+    arr = (ctypes.c_void_p * max(len(hs), 1))(*hs)
+    t = np.ascontiguousarray(tiers, dtype=np.uint32)
+    sl = np.ascontiguousarray(slots, dtype=np.uint32)
+    if t.ndim != 1 or t.shape != sl.shape:
+        raise ValueError("tiers and slots are parallel 1-d arrays, one entry per table")
+    return arr, len(hs), t, sl
+
+
+def probe_tiers(sets: Sequence[FilterSet], tiers, slots, keys, gated: bool = True, out=None, stream=None):
+    """The gate rows of an ordered table list whose filters live in several
+    FilterSets of different m (cb_tiers_probe_*): table t's filter and zone
+    are slot slots[t] of sets[tiers[t]]. Returns uint64[nt, ceil(n/64)], row
+    t = table t: what sets[tiers[t]].probe(keys, gated=gated) reports for slot
+    slots[t] (src/sstable.rs:138), with the key hashed once for every tier.
+    Up to 8 sets of width 32 or 64 and up to 64 tables."""
+    b = as_batch(keys)
+    arr, ns, t, sl = _tier_args(sets, tiers, slots)
+    nt = int(t.shape[0])
+    words = (b.n + 63) // 64
+    if out is None:
+        out = np.zeros((max(nt, 1), max(words, 1)), np.uint64)
+        result = out[:nt, :words]
+    else:
+        result = out
+    op, keep = _ptr_of(out)
+    s = _stream(stream)
+    ap = ctypes.cast(arr, ctypes.c_void_p)
+    if b.is_var:
+        dp, k1 = _ptr_of(b.data)
+        offp, k2 = _ptr_of(b.offsets)
+        _raise(_L().cb_tiers_probe_var(ap, ns, t.ctypes.data, sl.ctypes.data, nt, dp, offp, b.n, int(bool(gated)),
+                                       op, s))
+    else:
+        kp, k1 = _ptr_of(b.keys)
+        _raise(_L().cb_tiers_probe_fixed(ap, ns, t.ctypes.data, sl.ctypes.data, nt, kp, b.key_len, b.n,
+                                         int(bool(gated)), op, s))
+    return result
+
+
+def get_many_tiers(tables: Sequence[Table], sets: Sequence[FilterSet], tiers, slots, keys, stream=None, out=None,
+                   wait=True):
+    """Database::get in one launch over tiered filter sets
+    (cb_tiers_get_many_*): get_many's walk with table t's gate taken from
+    slot slots[t] of sets[tiers[t]] inside the search kernel, the key hashed
+    once for every tier. The store after a compaction: a large table behind
+    a large filter and fresh tables behind m = 1024 ones. Same return forms as
+    get_many (out=, wait=)."""
+    arr, ns, t, sl = _tier_args(sets, tiers, slots)
+    if len(tables) != int(t.shape[0]):
+        raise ValueError("tiers and slots need one entry per table")
+    L = _L()
+    head = (ctypes.cast(arr, ctypes.c_void_p), ns, ctypes.cast(_table_array(tables), ctypes.c_void_p), len(tables),
+            t.ctypes.data, sl.ctypes.data)
+    return _get_many_run(L.cb_tiers_get_many_fixed, L.cb_tiers_get_many_var, head, keys, stream, out, wait)
 
 
 def unpack_hits(hits: np.ndarray, n: int) -> np.ndarray:

@@ -926,9 +926,116 @@ int note_zone_read(const cb_filterset* set, hipStream_t s) {
   return CB_OK;
 }
 
+int tier_args(const TierList& tl, uint32_t nt, bool gated, cb::TierArgs* out, int* device) {
+  if (!tl.sets || !tl.tiers || !tl.slots) return fail(CB_EINVAL, "null argument");
+  if (tl.ns < 1 || tl.ns > cb::kMaxTiers) return fail(CB_EINVAL, "a tiered call takes 1 to 8 sets");
+  if (nt < 1 || nt > cb::kTierTables) return fail(CB_EINVAL, "a tiered call takes 1 to 64 tables");
+  for (uint32_t i = 0; i < tl.ns; ++i) {
+    const cb_filterset* set = tl.sets[i];
+    if (!set) return fail(CB_EINVAL, "null set");
+    if (set->width != 32 && set->width != 64) return fail(CB_EINVAL, "a tier is a set of 32 or 64 slots");
+    if (set->device != tl.sets[0]->device) return fail(CB_EINVAL, "tiers live on different devices");
+  }
+  cb::TierArgs ta;
+  std::memset(&ta, 0, sizeof ta);
+  ta.ns = tl.ns;
+  ta.nt = nt;
+  uint32_t count[cb::kMaxTiers] = {};
+  for (uint32_t t = 0; t < nt; ++t) {
+    const uint32_t i = tl.tiers[t], sl = tl.slots[t];
+    if (i >= tl.ns) return fail(CB_EINVAL, "tier out of range");
+    if (sl >= tl.sets[i]->width) return fail(CB_EINVAL, "slot out of range");
+    ta.tbl[t] = (uint16_t)(i << 8 | sl);
+    ta.tier[i].live |= 1ull << sl;
+    ++count[i];
+  }
+  // the tables grouped by tier (a counting sort: table order kept inside a tier)
+  uint32_t at[cb::kMaxTiers];
+  for (uint32_t i = 0, o = 0; i < cb::kMaxTiers; ++i) {
+    ta.start[i] = (uint8_t)o;
+    at[i] = o;
+    o += count[i];
+    ta.start[i + 1] = (uint8_t)o;
+  }
+  for (uint32_t t = 0; t < nt; ++t) ta.srt[at[tl.tiers[t]]++] = (uint16_t)(t << 8 | tl.slots[t]);
+  ta.all32 = 1;
+  int named = -1;
+  for (uint32_t i = 0; i < tl.ns; ++i) {
+    const cb_filterset* set = tl.sets[i];
+    cb::TierDesc& d = ta.tier[i];
+    if (!d.live) continue;
+    if (named < 0) named = (int)i;
+    d.words = set->words;
+    d.mp = set->mp;
+    d.generic = set->mode == cb::MOD_GENERIC ? ~0ull : 0ull;
+    d.half = set->width == 32 ? 1u : 0u;
+    if (set->mode != cb::MOD_POW2_32) ta.all32 = 0;
+    if (gated && set->zany) {
+      d.zv = set_zone_view(set);
+      d.zv.gated &= d.live;
+    }
+  }
+  for (uint32_t t = 0; t < nt; ++t)
+    if ((ta.tier[tl.tiers[t]].zv.gated >> tl.slots[t]) & 1ull) {
+      ta.tgated |= 1ull << t;
+      ta.zpre[t] = ta.tier[tl.tiers[t]].zv.pre + 2 * tl.slots[t];
+    }
+  // tiers no table names, and the entries past ns: a named tier's words with
+  // no live slot (in-bounds loads, and the unnamed set is never read)
+  for (uint32_t i = 0; i < cb::kMaxTiers; ++i) {
+    if (ta.tier[i].live) continue;
+    ta.tier[i] = ta.tier[named];
+    ta.tier[i].live = 0;
+    ta.tier[i].zv.gated = 0;
+  }
+  *out = ta;
+  *device = tl.sets[0]->device;
+  return CB_OK;
+}
+
+int note_tier_reads(const TierList& tl, const cb::TierArgs& ta, hipStream_t s) {
+  for (uint32_t i = 0; i < tl.ns; ++i)
+    if (ta.tier[i].zv.gated)
+      if (int rc = note_zone_read(tl.sets[i], s)) return rc;
+  return CB_OK;
+}
+
 }  // namespace cbx
 
 namespace {
+
+// cb_tiers_probe_*: the gate rows of a table list over tiered sets.
+int tiers_probe_impl(const TierList& tl, uint32_t nt, const uint8_t* keys, const uint64_t* offsets, uint32_t key_len,
+                     uint64_t n, bool gated, uint64_t* hits, hipStream_t s) {
+  cb::TierArgs ta;
+  int dev = 0;
+  if (int rc = tier_args(tl, nt, gated, &ta, &dev)) return rc;
+  if (n == 0) return CB_OK;
+  if (!hits) return fail(CB_EINVAL, "null hits");
+  if (offsets == nullptr && keys == nullptr && key_len) return fail(CB_EINVAL, "null keys");
+  DeviceGuard dg(dev);
+  Workspace& ws = workspace(dev, s);
+  std::lock_guard<std::mutex> lk(ws.mu);
+  StagedKeys sk;
+  int rc = offsets ? stage_var(ws, keys, offsets, n, s, sk) : stage_fixed(ws, keys, key_len, n, s, sk);
+  if (rc) return rc;
+  const uint64_t hwords = (n + 63) / 64;
+  uint64_t* dhits = hits;
+  const bool host_hits = !is_device_ptr(hits);
+  if (host_hits) {
+    HIP_TRY(ws.hits.reserve((size_t)nt * hwords * 8, s));
+    dhits = (uint64_t*)ws.hits.p;
+  }
+  HIP_TRY(cb::launch_tier_probe(sk.keyk, ta, sk.ks, n, dhits, hwords, s));
+  if ((rc = note_tier_reads(tl, ta, s))) return rc;
+  if (host_hits) {
+    HIP_TRY(hipMemcpyAsync(hits, dhits, (size_t)nt * hwords * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+  } else if (sk.staged) {
+    HIP_TRY(hipStreamSynchronize(s));
+  }
+  return CB_OK;
+}
 
 // Rebuild and upload the set's zone table (cb::ZoneView layout). Called on
 // zone updates, which happen once per table flush: the upload is ordered on
@@ -2145,6 +2252,20 @@ int cb_set_probe_gated_var(const cb_filterset* set, const uint8_t* bytes, const 
   return set_probe_impl(set, bytes, offsets, 0, n, hits, (hipStream_t)stream, true);
 }
 
+int cb_tiers_probe_fixed(const cb_filterset* const* sets, uint32_t ns, const uint32_t* tiers,
+                         const uint32_t* slots, uint32_t nt, const uint8_t* keys, uint32_t key_len, uint64_t n,
+                         int gated, uint64_t* hits, void* stream) {
+  return tiers_probe_impl(TierList{sets, ns, tiers, slots}, nt, keys, nullptr, key_len, n, gated != 0, hits,
+                          (hipStream_t)stream);
+}
+
+int cb_tiers_probe_var(const cb_filterset* const* sets, uint32_t ns, const uint32_t* tiers, const uint32_t* slots,
+                       uint32_t nt, const uint8_t* bytes, const uint64_t* offsets, uint64_t n, int gated,
+                       uint64_t* hits, void* stream) {
+  if (!offsets) return fail(CB_EINVAL, "null offsets");
+  return tiers_probe_impl(TierList{sets, ns, tiers, slots}, nt, bytes, offsets, 0, n, gated != 0, hits,
+                          (hipStream_t)stream);
+}
 
 int cb_filter_insert_fixed_many(cb_filter* const* filters, uint32_t nf, const uint8_t* const* keys,
                                 uint32_t key_len, const uint64_t* n, void* stream) {

@@ -23,6 +23,7 @@
 #include "kernels.hpp"
 #include "knobs.hpp"
 #include "sstable.hpp"
+#include "tierset.hpp"
 #include "wideset.hpp"
 #include "zone.hpp"
 
@@ -312,6 +313,20 @@ int set_probe_device(const cb_filterset* set, const uint8_t* keys, uint32_t key_
 
 // A launch that reads set's device zone table was enqueued on s (capi.cpp).
 int note_zone_read(const cb_filterset* set, hipStream_t s);
+
+// A tiered launch's sets and its table -> (tier, slot) mapping (cb_tiers_*).
+struct TierList {
+  const cb_filterset* const* sets;
+  uint32_t ns;
+  const uint32_t* tiers;
+  const uint32_t* slots;
+};
+// Checks a tier list for nt tables against the cb_tiers_* limits and fills
+// the kernels' argument from the sets as they are now (gated: with their
+// zone tables). Host work only; *device receives the sets' device.
+int tier_args(const TierList& tl, uint32_t nt, bool gated, cb::TierArgs* out, int* device);
+// note_zone_read for every tier whose zone table a launch with `ta` reads.
+int note_tier_reads(const TierList& tl, const cb::TierArgs& ta, hipStream_t s);
 
 // Device-accessible memory (hipMalloc, managed) is used in place; anything
 // else (pageable or pinned host memory) is staged by the library.

@@ -163,12 +163,21 @@ int wide_screen(Workspace& ws, const cb_table* const* tables, const std::vector<
 
 // set != NULL: the fused form (cb_set_get_many_*): the gate comes from the
 // FilterSet inside the search kernel, hit_rows are the tables' slots and
-// hits is unused.
+// hits is unused. tl != NULL: the same over tiered sets (cb_tiers_get_many_*):
+// table t's tier and slot come from the tier list, hits and hit_rows are unused.
 int get_many_impl(const cb_table* const* tables, uint32_t nt, const uint64_t* hits,
                   const uint32_t* hit_rows, const uint8_t* keys, const uint64_t* offsets,
                   uint32_t key_len, uint64_t n, int32_t* which, uint64_t* val_off, uint8_t* vals,
-                  uint64_t cap, uint64_t* total, hipStream_t s, const cb_filterset* set = nullptr) {
+                  uint64_t cap, uint64_t* total, hipStream_t s, const cb_filterset* set = nullptr,
+                  const TierList* tl = nullptr) {
   if (!which || !val_off || (nt && !tables)) return fail(CB_EINVAL, "null argument");
+  cb::TierArgs ta;
+  int tier_dev = 0;
+  if (tl) {
+    if (int rc = tier_args(*tl, nt, true, &ta, &tier_dev)) return rc;
+    hits = nullptr;
+    hit_rows = nullptr;
+  }
   if (set) {
     if (nt > set->width) return fail(CB_EINVAL, "more tables than the set's slots");
     if (hit_rows)
@@ -203,6 +212,7 @@ int get_many_impl(const cb_table* const* tables, uint32_t nt, const uint64_t* hi
     views[i] = tables[i]->view();
   }
   if (set && set->device != dev) return fail(CB_EINVAL, "set and tables live on different devices");
+  if (tl && tier_dev != dev) return fail(CB_EINVAL, "sets and tables live on different devices");
   std::vector<uint32_t> rows;
   if ((hits || set) && hit_rows) {
     rows.assign(hit_rows, hit_rows + nt);
@@ -324,6 +334,10 @@ int get_many_impl(const cb_table* const* tables, uint32_t nt, const uint64_t* hi
                                     set->zany ? &zv : nullptr, dviews, nt, drows, sk.ks, n, dwhich,
                                     (uint64_t*)ws.t_line.p, (uint64_t*)ws.t_dlen.p, tsum, s));
     if (set->zany && (rc = note_zone_read(set, s))) return rc;
+  } else if (tl) {
+    HIP_TRY(cb::launch_tier_get_many(sk.keyk, ta, dviews, sk.ks, n, dwhich, (uint64_t*)ws.t_line.p,
+                                     (uint64_t*)ws.t_dlen.p, tsum, s));
+    if ((rc = note_tier_reads(*tl, ta, s))) return rc;
   } else {
     HIP_TRY(cb::launch_get_many(sk.keyk, dviews, nt, dhits, drows, hwords, sk.ks, n, dwhich,
                                 (uint64_t*)ws.t_line.p, (uint64_t*)ws.t_dlen.p, tsum, s));
@@ -1259,6 +1273,25 @@ int cb_set_get_many_var(const cb_filterset* set, const cb_table* const* tables, 
   if (!offsets) return fail(CB_EINVAL, "null offsets");
   return get_many_impl(tables, nt, nullptr, slots, bytes, offsets, 0, n, which, val_off, vals, cap, total,
                        (hipStream_t)stream, set);
+}
+
+int cb_tiers_get_many_fixed(const cb_filterset* const* sets, uint32_t ns, const cb_table* const* tables,
+                            uint32_t nt, const uint32_t* tiers, const uint32_t* slots, const uint8_t* keys,
+                            uint32_t key_len, uint64_t n, int32_t* which, uint64_t* val_off, uint8_t* vals,
+                            uint64_t cap, uint64_t* total, void* stream) {
+  const TierList tl{sets, ns, tiers, slots};
+  return get_many_impl(tables, nt, nullptr, nullptr, keys, nullptr, key_len, n, which, val_off, vals, cap, total,
+                       (hipStream_t)stream, nullptr, &tl);
+}
+
+int cb_tiers_get_many_var(const cb_filterset* const* sets, uint32_t ns, const cb_table* const* tables, uint32_t nt,
+                          const uint32_t* tiers, const uint32_t* slots, const uint8_t* bytes,
+                          const uint64_t* offsets, uint64_t n, int32_t* which, uint64_t* val_off, uint8_t* vals,
+                          uint64_t cap, uint64_t* total, void* stream) {
+  if (!offsets) return fail(CB_EINVAL, "null offsets");
+  const TierList tl{sets, ns, tiers, slots};
+  return get_many_impl(tables, nt, nullptr, nullptr, bytes, offsets, 0, n, which, val_off, vals, cap, total,
+                       (hipStream_t)stream, nullptr, &tl);
 }
 
 }  // extern "C"

@@ -147,20 +147,6 @@ __global__ __launch_bounds__(256) void k_set_put_slot(const uint32_t* __restrict
 
 constexpr uint32_t kSetProbeThreads = 64 * kSetWords;  // one 64-key hit word per wave
 
-// The wave's 64 keys' masks -> lane f holds slot f's 64-key hit word.
-template <int W, class word_t>
-__device__ __forceinline__ uint64_t slot_words(word_t mask, uint32_t used, uint32_t lane) {
-  uint64_t mine = 0;
-#pragma unroll
-  for (uint32_t f = 0; f < (uint32_t)W; ++f) {
-    if (f < used) {
-      const uint64_t bal = __ballot((mask >> f) & 1u);
-      mine = (lane == f) ? bal : mine;
-    }
-  }
-  return mine;
-}
-
 // The block's hit positions into the exchange pack (PackSink): the block's
 // set bits are counted (one entry per thread: thread i = slot i / 16, word
 // i % 16), one relaxed atomic add claims their slots (low half: slots, high

@@ -90,6 +90,21 @@ __device__ __forceinline__ void stage_zone_prefixes(const ZoneView& zv, BoundPre
   }
 }
 
+// The wave's 64 keys' masks -> lane f holds slot f's 64-key hit word (the
+// probes' ballot step: filterset.hip, tierset.hip).
+template <int W, class word_t>
+__device__ __forceinline__ uint64_t slot_words(word_t mask, uint32_t used, uint32_t lane) {
+  uint64_t mine = 0;
+#pragma unroll
+  for (uint32_t f = 0; f < (uint32_t)W; ++f) {
+    if (f < used) {
+      const uint64_t bal = __ballot((mask >> f) & 1u);
+      mine = (lane == f) ? bal : mine;
+    }
+  }
+  return mine;
+}
+
 // Every (key kind, hash mode, set width) instantiation, by runtime values.
 #define CB_SET_DISPATCH(keyk, mode, width, CALL)                                              \
   switch (((keyk) * 3 + (mode)) * 2 + ((width) == 64)) {                                     \

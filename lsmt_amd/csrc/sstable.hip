@@ -21,6 +21,7 @@
 #include "profile.hpp"
 #include "setmask.hpp"
 #include "sstable.hpp"
+#include "tiermask.hpp"
 #include "wideset.hpp"
 #include "zone.hpp"
 
@@ -933,6 +934,45 @@ __global__ __launch_bounds__(kNT, 6) void k_set_get_many(const void* __restrict_
   if (threadIdx.x == 0) tsum[blockIdx.x] = total;
 }
 
+// Database::get in one launch over tiered filter sets (tierset.hpp): the
+// store after a compaction, whose tables' filters live in FilterSets of
+// different m. k_set_get_many with tier_key_mask in place of set_key_mask:
+// the key is hashed once for every tier and the result is already in table
+// order, so it is the candidate word. nt <= 64: one group.
+template <int KEYK, bool ALL32, int NS>
+__global__ __launch_bounds__(kNT, 6) void k_tier_get_many(TierArgs ta, const TableView* __restrict__ tv, KeySrc ks,
+                                                          uint64_t n, int32_t* __restrict__ which,
+                                                          uint64_t* __restrict__ vsrc, uint64_t* __restrict__ dlen,
+                                                          uint64_t* __restrict__ tsum) {
+  const uint64_t k = (uint64_t)blockIdx.x * kNT + threadIdx.x;
+  const uint32_t nt = ta.nt;
+  const ViewRegs vr = load_views(tv, nt);
+  __shared__ BoundPrefix zp[2 * kTierTables];
+  __shared__ uint16_t stbl[kTierTables], ssrt[kTierTables];
+  __shared__ TableView stv[64];
+  __shared__ DirMap sdm[64];
+  stage_tier_lists(ta, stbl, ssrt);
+  stage_tier_prefixes<KEYK>(ta, zp, kNT);
+  // the key's loads go out before the barrier (k_set_get_many: after it, the
+  // compiler kept the whole search's state live across the gate)
+  const Query q = make_query<KEYK>(ks, k < n ? k : 0);
+  store_views(vr, nt, stv);  // barrier: views, table lists and zone prefixes staged
+  const uint64_t cand0 = tier_key_mask<KEYK, ALL32, NS, false>(ta, stbl, ssrt, ks, k, k < n, zp);
+  stage_maps(stv, nt, sdm);
+  uint64_t d = 0;
+  if (k < n) {
+    int32_t w = -1;
+    uint64_t src = 0;
+    (void)resolve_group<true>(stv, tv, sdm, 0, cand0, q, w, src, d);
+    which[k] = w;
+    vsrc[k] = src;
+    dlen[k] = d;
+  }
+  uint64_t total;
+  (void)block_scan<kNT>(d, &total);
+  if (threadIdx.x == 0) tsum[blockIdx.x] = total;
+}
+
 // The wide walk's screen (wideset.hpp WideScreen): bit (B, h, slot) is clear
 // only when the table in that slot has a complete key bucket B none of whose
 // stored fingerprints falls in bin h (fp & (H - 1)). One thread per (table,
@@ -1559,6 +1599,22 @@ hipError_t launch_set_get_many(int keyk, int mode, uint32_t width, const void* s
   ProfScope ps("k_set_get_many", s);
   CB_SET_DISPATCH(keyk, mode, width,
                   (set_get_many<KK, MM, WW>(set, mp, zv, tv, nt, slots, ks, n, which, vsrc, dlen, tsum, s)));
+  return hipGetLastError();
+}
+
+template <int KK, bool AA, int NN>
+static void tier_get_many(const TierArgs& ta, const TableView* tv, const KeySrc& ks, uint64_t n, int32_t* which,
+                          uint64_t* vsrc, uint64_t* dlen, uint64_t* tsum, hipStream_t s) {
+  hipLaunchKernelGGL((k_tier_get_many<KK, AA, NN>), dim3(blocks_for(n, kNT)), dim3(kNT), 0, s, ta, tv, ks, n, which,
+                     vsrc, dlen, tsum);
+}
+
+hipError_t launch_tier_get_many(int keyk, const TierArgs& ta, const TableView* tv, const KeySrc& ks, uint64_t n,
+                                int32_t* which, uint64_t* vsrc, uint64_t* dlen, uint64_t* tsum, hipStream_t s) {
+  if (!n) return hipSuccess;
+  if (!ta.nt || ta.nt > kTierTables || !ta.ns || ta.ns > kMaxTiers) return hipErrorInvalidValue;
+  ProfScope ps("k_tier_get_many", s);
+  CB_TIER_DISPATCH(keyk, ta.all32, ta.ns, (tier_get_many<KK, AA, NN>(ta, tv, ks, n, which, vsrc, dlen, tsum, s)));
   return hipGetLastError();
 }
 

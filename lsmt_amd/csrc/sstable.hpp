@@ -12,6 +12,7 @@
 #include <stdint.h>
 
 #include "hash.hpp"
+#include "tierset.hpp"
 #include "zone.hpp"
 
 namespace cb {
@@ -426,6 +427,12 @@ hipError_t launch_set_get_many(int keyk, int mode, uint32_t width, const void* s
                                const ZoneView* zones, const TableView* tv, uint32_t nt, const uint32_t* slots,
                                const KeySrc& ks, uint64_t n, int32_t* which, uint64_t* vsrc, uint64_t* dlen,
                                uint64_t* tsum, hipStream_t s);
+// Database::get in one launch over tiered filter sets (tierset.hpp: table t
+// is slot ta.tbl[t] & 63 of tier ta.tbl[t] >> 8, the key hashed once for all
+// tiers), then the same walk and outputs as launch_get_many; tv holds ta.nt
+// views, ta.nt <= 64.
+hipError_t launch_tier_get_many(int keyk, const TierArgs& ta, const TableView* tv, const KeySrc& ks, uint64_t n,
+                                int32_t* which, uint64_t* vsrc, uint64_t* dlen, uint64_t* tsum, hipStream_t s);
 // Database::get in one launch over a WIDE set (wideset.hpp: more than 64
 // slots, R = W/64 words per row): the groups of 64 tables (newest first)
 // take their candidate bits from windows of rows a and b (groups[g], the
