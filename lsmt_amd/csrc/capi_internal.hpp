@@ -1,7 +1,10 @@
-// capi_internal.hpp — what the C ABI's translation units share (capi.cpp:
-// filters, probes, sets, codec, exchange; capi_sstable.cpp: SSTable files,
-// the read path and SsTable::create): the handle structs, error reporting,
-// device buffers, the block pool, per-stream workspaces and key staging.
+// capi_internal.hpp — what the C ABI's translation units share
+// (capi_runtime.cpp: errors, the block pool, workspaces, staging;
+// capi_filter.cpp: filters, insert / probe, the codec's device halves;
+// capi_set.cpp: filter sets, zones, tiers, the exchange entries;
+// capi_sstable.cpp: SSTable files, the read path and SsTable::create): the
+// handle structs, error reporting, device buffers, the block pool, per-stream
+// workspaces and the host frame around a keyed launch.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -62,7 +65,7 @@ struct cb_filter {
   std::atomic<uint64_t> gen{1};       // bumped by every write to words
   std::atomic<uint64_t> host_gen{0};  // the gen `host` holds
   std::mutex host_mu;                 // one refresh at a time
-  std::mutex zero_mu;                 // the lazy clear's issue vs. a refresh (capi.cpp ensure_zeroed)
+  std::mutex zero_mu;                 // the lazy clear's issue vs. a refresh (capi_filter.cpp ensure_zeroed)
   std::vector<uint32_t> host;         // ceil(m/32) words
   // recorded after the last device write made with the mirror on
   // (atomic_load / atomic_store). Writes from several streams are ordered by
@@ -71,7 +74,7 @@ struct cb_filter {
   std::shared_ptr<WriteMark> wmark;
   // a write was made with the mirror off (nothing recorded, no stream handle
   // kept: VERDICT r5): the refresh waits for every stream the library knows
-  // on the device, by events (capi.cpp wait_known_streams)
+  // on the device, by events (capi_runtime.cpp wait_known_streams)
   std::atomic<bool> unmarked{false};
   // -1 auto (m <= kMirrorAutoBits), 0 off, 1 on; read by concurrent `&self`
   // callers (cb_may_contain, probes) while cb_filter_host_mirror may write it
@@ -115,13 +118,13 @@ struct cb_filterset {
   // Readers of the device zone table: one event per stream, recorded after
   // every launch that reads it (gated probes, the fused read path). A zone
   // update waits for these events — the streams' last readers — instead of
-  // the whole device, then rewrites the table (capi.cpp upload_zones).
+  // the whole device, then rewrites the table (capi_set.cpp upload_zones).
   mutable std::mutex zmu;
   mutable std::map<hipStream_t, hipEvent_t> zread;
   std::vector<void*> zretired;  // outgrown tables, freed by cb_set_destroy
 };
 
-// The device zone table of a set (capi.cpp upload_zones): 64 cb::ZoneView
+// The device zone table of a set (capi_set.cpp upload_zones): 64 cb::ZoneView
 // headers, then the bounds' 16-byte prefixes, then the bound bytes.
 constexpr size_t cb_zone_hdr_bytes = 64 * 16;
 constexpr size_t cb_zone_pre_bytes = 64 * 2 * sizeof(cb::BoundPrefix);
@@ -254,7 +257,7 @@ struct DevBuf {
   }
 };
 
-// Device block pool for table, filter and set storage (capi.cpp). *cap
+// Device block pool for table, filter and set storage (capi_runtime.cpp). *cap
 // receives the block's size (pass it back to pool_release). Release is
 // stream-ordered: the block is retired behind an event on every stream the
 // library knows on that device and reused only once they have all completed;
@@ -311,8 +314,10 @@ int compress_state(Workspace& ws, hipStream_t s, cb::CompressState** out);
 int set_probe_device(const cb_filterset* set, const uint8_t* keys, uint32_t key_len, uint64_t n, bool gated,
                      uint64_t* hits, uint32_t* sink_pack, uint64_t cap, hipStream_t s);
 
-// A launch that reads set's device zone table was enqueued on s (capi.cpp).
+// A launch that reads set's device zone table was enqueued on s (capi_set.cpp).
 int note_zone_read(const cb_filterset* set, hipStream_t s);
+// Does a probe of `set` asked to be gated read its zone table?
+inline bool gate_on(const cb_filterset* set, bool gated) { return gated && set->zany; }
 
 // A tiered launch's sets and its table -> (tier, slot) mapping (cb_tiers_*).
 struct TierList {
@@ -328,9 +333,14 @@ int tier_args(const TierList& tl, uint32_t nt, bool gated, cb::TierArgs* out, in
 // note_zone_read for every tier whose zone table a launch with `ta` reads.
 int note_tier_reads(const TierList& tl, const cb::TierArgs& ta, hipStream_t s);
 
+// What kind of memory p is: one pointer-attribute query (NULL and pointers
+// the runtime does not know are pageable host memory).
+enum MemKind { MEM_PAGEABLE = 0, MEM_PINNED, MEM_DEVICE };
+MemKind mem_kind(const void* p);
 // Device-accessible memory (hipMalloc, managed) is used in place; anything
 // else (pageable or pinned host memory) is staged by the library.
-bool is_device_ptr(const void* p);
+inline bool is_device_ptr(const void* p) { return mem_kind(p) == MEM_DEVICE; }
+inline bool is_pinned_host(const void* p) { return mem_kind(p) == MEM_PINNED; }
 
 struct DeviceGuard {
   int prev = -1;
@@ -350,10 +360,40 @@ struct StagedKeys {
   bool staged = false;
 };
 
-int stage_fixed(Workspace& ws, const uint8_t* keys, uint32_t key_len, uint64_t n, hipStream_t s,
-                StagedKeys& out);
-int stage_var(Workspace& ws, const uint8_t* bytes, const uint64_t* offsets, uint64_t n,
-              hipStream_t s, StagedKeys& out);
+// The host frame around a keyed launch ("keys in, rows out"): refuse null
+// keys, stage the keys, take the output in place or in a workspace buffer
+// (out_buf below), launch, then finish_out.
+
+// The refusal of a fixed-length batch without keys. stage_keys makes it;
+// an entry point with other refusals between its argument checks and its
+// staging calls it where the check has always stood.
+int null_keys(const uint8_t* keys, const uint64_t* offsets, uint32_t key_len);
+// Keys as the kernels see them (device pointers): var keys when offsets is
+// given, else fixed-length ones; host keys are staged in ws (ws.mu held).
+int stage_keys(Workspace& ws, const uint8_t* keys, const uint64_t* offsets, uint32_t key_len, uint64_t n,
+               hipStream_t s, StagedKeys& out);
+// The one rule for the 16-byte key loads: 16-byte keys from a 16-byte
+// aligned base.
+inline int fixed_keyk(const void* p, uint32_t key_len) {
+  return (key_len == 16 && !((uintptr_t)p & 15)) ? cb::KEY_FIXED16 : cb::KEY_FIXED;
+}
+// The keys of a staged batch from key k0 on (sk.keyk holds for the slice).
+inline KeySrc slice_keys(const StagedKeys& sk, uint64_t k0) {
+  KeySrc ks = sk.ks;
+  if (sk.keyk == cb::KEY_VAR)
+    ks.offsets += k0;
+  else
+    ks.bytes += k0 * ks.key_len;  // KEY_FIXED16 stays right: an aligned base plus a multiple of 16
+  return ks;
+}
+// The end of a keyed call: rows that were produced in a workspace buffer
+// (dev != user) are copied back and waited for; rows written in place need
+// the wait only when staged host keys are still being read.
+int finish_out(void* user, const void* dev, size_t bytes, bool staged, hipStream_t s);
+
+// The pending lazy clear of f (cb_filter_clear, a new filter), issued on s by
+// whichever operation needs the words first (capi_filter.cpp).
+hipError_t ensure_zeroed(const cb_filter* f, hipStream_t s);
 // A batched insert with the stream's workspace already locked by the caller.
 int insert_locked(Workspace& ws, cb_filter* f, const uint8_t* keys, const uint64_t* offsets,
                   uint32_t key_len, uint64_t n, hipStream_t s);

@@ -40,23 +40,16 @@ int table_search_impl(const cb_table* t, const uint8_t* keys, const uint64_t* of
   if (!t || !line_out) return fail(CB_EINVAL, "null argument");
   if (int rc = finalize_table(const_cast<cb_table*>(t))) return rc;
   if (n == 0) return CB_OK;
-  if (offsets == nullptr && keys == nullptr && key_len) return fail(CB_EINVAL, "null keys");
   DeviceGuard dg(t->device);
   Workspace& ws = workspace(t->device, s);
   std::lock_guard<std::mutex> lk(ws.mu);
   StagedKeys sk;
-  int rc = offsets ? stage_var(ws, keys, offsets, n, s, sk) : stage_fixed(ws, keys, key_len, n, s, sk);
+  int rc = stage_keys(ws, keys, offsets, key_len, n, s, sk);
   if (rc) return rc;
   int64_t* dl;
   if ((rc = out_buf(ws.t_line, line_out, n, s, &dl))) return rc;
   HIP_TRY(cb::launch_table_search(sk.keyk, t->view(), sk.ks, n, dl, s));
-  if (dl != line_out) {
-    HIP_TRY(hipMemcpyAsync(line_out, dl, n * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-  } else if (sk.staged) {
-    HIP_TRY(hipStreamSynchronize(s));
-  }
-  return CB_OK;
+  return finish_out(line_out, dl, n * 8, sk.staged, s);
 }
 
 bool buckets_enabled() {
@@ -200,7 +193,7 @@ int get_many_impl(const cb_table* const* tables, uint32_t nt, const uint64_t* hi
     }
     return put_bytes((uint8_t*)val_off, &z, 8);
   }
-  if (offsets == nullptr && keys == nullptr && key_len) return fail(CB_EINVAL, "null keys");
+  if (int rc = null_keys(keys, offsets, key_len)) return rc;  // (here: ahead of the table checks)
   if (nt == 0) return fail(CB_EINVAL, "no tables");
   const int dev = tables[0] ? tables[0]->device : 0;
   std::vector<cb::TableView> views(nt);
@@ -225,7 +218,7 @@ int get_many_impl(const cb_table* const* tables, uint32_t nt, const uint64_t* hi
   Workspace& ws = workspace(dev, s);
   std::lock_guard<std::mutex> lk(ws.mu);
   StagedKeys sk;
-  int rc = offsets ? stage_var(ws, keys, offsets, n, s, sk) : stage_fixed(ws, keys, key_len, n, s, sk);
+  int rc = stage_keys(ws, keys, offsets, key_len, n, s, sk);
   if (rc) return rc;
   const uint64_t hwords = (n + 63) / 64;
   const uint64_t* dhits = hits;

@@ -30,7 +30,7 @@
 // the entries cost one 8-B round trip per key, and set[b] stays a random read
 // for the ~45 % of keys whose set[a] is non-zero. Regions are dealt to XCDs
 // in contiguous ranges, so the run lines adjacent regions share are fetched
-// once per XCD. Selected by density (capi.cpp set_probe_*); results are the
+// once per XCD. Selected by density (capi_set.cpp launch_set); results are the
 // same bits, checked against the oracle (tests/test_dense_probe_gpu.py).
 #include <hip/hip_runtime.h>
 

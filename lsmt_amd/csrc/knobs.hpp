@@ -13,9 +13,9 @@
 //                 product kernel carries an argument or a branch for them.
 //
 // Runtime (environment of an experiment build):
-//   CB_POOL_SLAB=0      capi.cpp: small pool requests get their own blocks
-//   CB_POOL_CONTIG=1    capi.cpp: pool memory physically contiguous
-//   CB_BUILD_BATCH=n    capi.cpp: filters per batched build launch pair
+//   CB_POOL_SLAB=0      capi_runtime.cpp: small pool requests get their own blocks
+//   CB_POOL_CONTIG=1    capi_runtime.cpp: pool memory physically contiguous
+//   CB_BUILD_BATCH=n    capi_filter.cpp: filters per batched build launch pair
 //   CB_NO_BUCKETS=1     capi_sstable.cpp: reads without the key buckets
 //   CB_NO_SCREEN=1      capi_sstable.cpp: wide reads without the screen
 //   CB_SCREEN_HBITS=h   capi_sstable.cpp: the wide screen's hash bits (0..8)

@@ -6,7 +6,7 @@ Reference semantics: BloomFilter::hashes / insert / may_contain
 (/root/reference/src/bloom.rs:26-51) for every table of Database::get's
 fan-out (src/lib.rs:129-134).
 
-What the shapes reach (lsmt_amd/csrc/kernels.hip, capi.cpp, densefs.hip):
+What the shapes reach (lsmt_amd/csrc/kernels.hip, capi_filter.cpp, capi_set.cpp, densefs.hip):
   * k_tile_probe<8,4,2>, the 2^18-bit tile with the two-deep register ring
     (plan_probe picks it for m >= 2^27 and n <= m/64): P1, P2, P6, P7, P8;
   * k_tile_probe<8,2,4> (tb = 17) with generic m, ragged keys, a partial last

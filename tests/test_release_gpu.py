@@ -5,7 +5,7 @@ keep reading under `sstables.read()` (/root/reference/src/lib.rs:21,129). Round
 5's pool_release ran hipDeviceSynchronize on every destroy, so one Drop
 stalled every stream of the process. Now a destroyed handle's block is
 retired behind an event on each stream the library has seen and handed out
-again only once those events have completed (capi.cpp pool_release / reap):
+again only once those events have completed (capi_runtime.cpp pool_release / reap):
 
 - a probe loop on one stream keeps its device step time while another
   thread's handles are destroyed between its launches;
@@ -190,7 +190,7 @@ def test_set_destroy_is_stream_ordered(gpu):
 
 def test_small_block_not_reused_under_a_queued_reader(gpu):
     """The same as above for a filter small enough to come from a slab
-    (m = 2^16: 8 KiB, capi.cpp pool_alloc's small blocks): the queued probe
+    (m = 2^16: 8 KiB, capi_runtime.cpp pool_alloc's small blocks): the queued probe
     reads A's bits, B's build gets another block or A's after the probe."""
     import torch
     m = 1 << 16

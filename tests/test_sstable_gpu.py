@@ -406,6 +406,29 @@ def test_search_device_resident(gpu):
     assert np.array_equal(srt[got], keys[::-1])
 
 
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 257])
+def test_search_host_var_keys_into_device_lines(gpu, n):
+    """Host ragged keys (staged by the library) with the line indices written
+    in place to device memory: the call returns only once the staged keys have
+    been read, so the caller may reuse its key buffers at once."""
+    import torch
+    rng = np.random.default_rng(n)
+    keys = workload.key_range(40, 300)
+    data = workload.sstable_bytes(keys, workload.table_value(keys, 2)).tobytes()
+    t, ot = gpu.Table(data), oracle.OracleTable(data)
+    look = [bytes(keys[i]) for i in rng.integers(0, 300, n)]
+    look = [k if i % 3 else k[: i % 16] for i, k in enumerate(look)]  # present keys, cut keys and the empty key
+    d, o = var(look)
+    exp = [ot.search(k)[0] for k in look]
+    out = torch.full((n,), -7, dtype=torch.int64, device="cuda")
+    t.search(gpu.KeyBatch(n=n, data=d, offsets=o), out=out)
+    d[:] = 0
+    o[:] = 0
+    torch.cuda.synchronize()
+    assert out.cpu().tolist() == exp
+    assert any(e >= 0 for e in exp) or n == 1
+
+
 def test_get_many_device_out_cap(gpu):
     # device output buffers: one pass; a value buffer smaller than the total is
     # left untouched and the total is still reported (then the caller retries)

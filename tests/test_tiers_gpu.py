@@ -201,6 +201,32 @@ def test_batch_edges(base16, n):
     assert np.array_equal(which, ow) and np.array_equal(voff, ovoff) and vals == ovals
 
 
+@pytest.fixture(scope="module", params=["k16", "ragged"])
+def small(request, gpu):
+    """Two tiers of the product's filter size and its odd neighbour."""
+    return Case(gpu, request.param, [(1000, 32), (1024, 64)], [0, 1, 0, 1], [3, 40, 31, 63], [60, 60, 60, 60],
+                seed=33, pool_n=3000, windows=[300, 300, 300, 300])
+
+
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 257])
+def test_host_keys_into_device_hits(small, n):
+    """Host keys (staged by the library) with the gate rows written in place
+    to device memory: the call returns only once the staged keys have been
+    read, so the caller may reuse its key buffer at once."""
+    import torch
+    c = small
+    look = c.look[:n]
+    for gated in (True, False):
+        want = c.oracle_gate(look, gated=gated)
+        kb = batch(c.gpu, look, c.kind)
+        hits = torch.full((c.nt, (n + 63) // 64), -1, dtype=torch.int64, device="cuda")
+        c.gpu.probe_tiers(c.sets, c.tiers, c.slots, kb, gated=gated, out=hits)
+        for a in (kb.data, kb.offsets) if c.kind == "ragged" else (kb,):
+            a[:] = 0
+        torch.cuda.synchronize()
+        assert np.array_equal(hits.cpu().numpy().view(np.uint64), want), gated
+
+
 def test_one_tier_equals_the_set_calls(gpu, base16):
     """ns = 1: bit for bit cb_set_probe_gated_* / cb_set_get_many_* on that set."""
     c = base16

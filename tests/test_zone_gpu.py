@@ -294,3 +294,42 @@ def test_zone_update_waits_for_gated_probes_on_other_streams(gpu):
     for out in before:
         assert np.array_equal(out.cpu().numpy().view(np.uint64), exp_full)
     assert np.array_equal(after, exp_narrow)
+
+
+@pytest.mark.parametrize("width", [32, 64])
+@pytest.mark.parametrize("m", [1000, 1024])
+def test_zone_gate_zero_copy_matches_oracle(gpu, m, width):
+    """The gated probe with pinned keys in and pinned hit rows out on a 32- /
+    64-slot set (the kernel reads and writes them in place, last_path 4):
+    16-byte keys and another length, slots with and without a zone, batch
+    sizes around the 64-key hit word."""
+    import torch
+    for length in (16, 11):
+        full = workload.zone_tables(4, 700, 300)
+        tables = [t[:, :length].copy() for t in full]
+        filters, refs, ozones = [], [], []
+        for t in tables:
+            b = gpu.BloomFilter(m)
+            b.insert_batch(t)
+            o = oracle.OracleFilter(m)
+            o.insert_fixed(t)
+            filters.append(b)
+            refs.append(o)
+        s = gpu.FilterSet.from_filters(filters, width=width)
+        for i, t in enumerate(tables[:3]):  # the last slot has no zone: it accepts every key
+            srt = sorted(bytes(r) for r in t)
+            s.set_zone(i, (srt[0], srt[-1]))
+            ozones.append(oracle.OracleZone(srt[0], srt[-1]))
+        ozones.append(None)
+        look = np.ascontiguousarray(workload.zone_lookups(full, 258)[:, :length])
+        for n in (1, 63, 64, 65, 257):
+            lk = look[:n]
+            offs = np.arange(0, length * (n + 1), length, dtype=np.uint64)
+            exp = oracle.probe_gated(refs, ozones, np.ascontiguousarray(lk.reshape(-1)), offs)
+            keys = torch.from_numpy(lk.copy()).pin_memory()
+            out = torch.full((4, (n + 63) // 64), -1, dtype=torch.int64).pin_memory()
+            s.probe(gpu.KeyBatch(n=n, key_len=length, keys=keys), out=out, gated=True)
+            assert gpu.last_path() == 4, (length, n)
+            assert np.array_equal(out.numpy().view(np.uint64), exp), (length, n)
+            if n == 257:  # the gate is not vacuous: it removes Bloom candidates
+                assert not np.array_equal(exp, oracle.probe_fixed(refs, lk))
