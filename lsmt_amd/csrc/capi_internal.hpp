@@ -269,16 +269,14 @@ struct Workspace {
   std::mutex mu;
   DevBuf keys, offsets, hits, seg, ent, masks, bools, lkey, zone;
   DevBuf t_views, t_rows, t_which, t_line, t_dlen, t_voff, t_scan, t_vals;
-  // what t_views / t_rows hold (a call with the same tables and rows uploads nothing)
-  std::vector<uint8_t> t_views_host;
-  std::vector<uint32_t> t_rows_host;
+  // what t_views / t_rows / t_groups hold, as bytes (a call with the same
+  // tables, rows and groups uploads nothing: capi_sstable.cpp upload_if_changed)
+  std::vector<uint8_t> t_views_host, t_rows_host, t_groups_host;
   DevBuf t_groups;                          // a wide set's table groups (cb::WideGroup)
   DevBuf t_maps;                            // the tables' DirMaps, contiguous (the wide walk stages them)
   std::vector<uint64_t> t_maps_sig;         // what t_maps was gathered from (table uids and map pointers)
   DevBuf w_scr;                             // the wide walk's screen (sstable.hpp WideScreen)
   std::vector<uint64_t> w_scr_sig;          // what it was built from (table uids, slots, buckets)
-  uint32_t w_scr_bits = 0, w_scr_hbits = 0;
-  std::vector<uint8_t> t_groups_host;
   DevBuf i_cnt, i_base, i_tmp, i_end, i_err, i_start;                 // line indexing
   DevBuf f_sk2, f_sort, f_tsum, f_flag, f_vsp;  // SsTable::create
   DevBuf x_ctl;                   // cb_hits_compress: slot / finish counters (zeroed once)

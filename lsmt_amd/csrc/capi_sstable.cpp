@@ -103,6 +103,74 @@ int table_buckets(cb_table* t, hipStream_t s, cb::TableView* v) {
   return CB_OK;
 }
 
+// How a get chooses each key's candidate tables. Each C entry pair builds
+// its own; a field that is not its kind's stays NULL.
+struct Gate {
+  enum Kind { ROWS, SET, TIERS } kind;
+  // ROWS (cb_get_many_*): table t is asked where hits has bit k of row
+  // rows[t] (hits NULL: every table; then rows is not read)
+  const uint64_t* hits;
+  // ROWS: the tables' hit rows; SET: their slots (NULL: table t is row / slot t)
+  const uint32_t* rows;
+  // SET (cb_set_get_many_*): the gate comes from the FilterSet inside the
+  // search kernel; a wide set takes the wide walk
+  const cb_filterset* set;
+  // TIERS (cb_tiers_get_many_*): the same over tiered sets, table t's tier
+  // and slot from the list
+  const TierList* tiers;
+  static Gate of_rows(const uint64_t* hits, const uint32_t* rows) { return {ROWS, hits, rows, nullptr, nullptr}; }
+  static Gate of_set(const cb_filterset* set, const uint32_t* slots) { return {SET, nullptr, slots, set, nullptr}; }
+  static Gate of_tiers(const TierList* tl) { return {TIERS, nullptr, nullptr, nullptr, tl}; }
+};
+
+// Where a get's answers go (cassbloom.h cb_get_many_*). total == NULL:
+// enqueue only (every buffer on the device; val_off[n] = the total).
+struct GetOut {
+  int32_t* which;
+  uint64_t* val_off;
+  uint8_t* vals;
+  uint64_t cap;
+  uint64_t* total;
+  bool async() const { return total == nullptr; }
+};
+
+// The device side of one get: the tables' views and rows / slots, the
+// answers (in place or in the workspace) and the value tail's scratch.
+struct GetBufs {
+  const cb::TableView* views;
+  const uint32_t* rows;  // NULL: identity
+  int32_t* which;
+  uint64_t* voff;
+  uint64_t *vsrc, *dlen, *tsum;
+};
+
+// The read path's two cache checks. Both are stream-ordered: earlier launches
+// on s have read the old contents before new ones land.
+
+// buf holds the bytes at src; uploaded only when they differ from `shadow`,
+// the host copy of what buf holds (a call with the same tables, rows or
+// groups uploads nothing).
+int upload_if_changed(DevBuf& buf, std::vector<uint8_t>& shadow, const void* src, size_t bytes, hipStream_t s) {
+  const uint8_t* b = (const uint8_t*)src;
+  if (shadow.size() == bytes && !memcmp(shadow.data(), b, bytes)) return CB_OK;
+  HIP_TRY(buf.reserve(bytes, s));
+  HIP_TRY(hipMemcpyAsync(buf.p, b, bytes, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipStreamSynchronize(s));  // the source is pageable
+  shadow.assign(b, b + bytes);
+  return CB_OK;
+}
+
+// Device data made from the tables (the wide walk's screen and its copy of
+// the maps): rebuilt by `build` when `sig`, what it would be made from now,
+// differs from `held`, what it was made from.
+template <class Build>
+int rebuild_if_changed(std::vector<uint64_t>& held, std::vector<uint64_t>& sig, Build build) {
+  if (sig == held) return CB_OK;
+  if (int rc = build()) return rc;
+  held.swap(sig);
+  return CB_OK;
+}
+
 // The wide walk's screen for these tables in these slots (sstable.hpp
 // WideScreen): built on s after their buckets, and kept in the stream's
 // workspace until the tables, their slots or their buckets change (compared
@@ -144,230 +212,271 @@ int wide_screen(Workspace& ws, const cb_table* const* tables, const std::vector<
     sig.push_back((uint64_t)(uintptr_t)views[i].bkt);
     sig.push_back(views[i].meta);
   }
-  if (sig != ws.w_scr_sig) {
-    HIP_TRY(ws.w_scr.reserve(cb::wide_screen_bytes(R, bits, hbits), s));
-    HIP_TRY(cb::launch_wide_screen(dviews, rows.empty() ? nullptr : drows, nt, R, bits, hbits,
-                                   (uint64_t*)ws.w_scr.p, s));
-    ws.w_scr_sig.swap(sig);
-  }
+  if (int rc = rebuild_if_changed(ws.w_scr_sig, sig, [&]() -> int {
+        HIP_TRY(ws.w_scr.reserve(cb::wide_screen_bytes(R, bits, hbits), s));
+        HIP_TRY(cb::launch_wide_screen(dviews, rows.empty() ? nullptr : drows, nt, R, bits, hbits,
+                                       (uint64_t*)ws.w_scr.p, s));
+        return CB_OK;
+      }))
+    return rc;
   *out = cb::WideScreen{(const uint64_t*)ws.w_scr.p, bits, hbits, 0};
   return CB_OK;
 }
 
-// set != NULL: the fused form (cb_set_get_many_*): the gate comes from the
-// FilterSet inside the search kernel, hit_rows are the tables' slots and
-// hits is unused. tl != NULL: the same over tiered sets (cb_tiers_get_many_*):
-// table t's tier and slot come from the tier list, hits and hit_rows are unused.
-int get_many_impl(const cb_table* const* tables, uint32_t nt, const uint64_t* hits,
-                  const uint32_t* hit_rows, const uint8_t* keys, const uint64_t* offsets,
-                  uint32_t key_len, uint64_t n, int32_t* which, uint64_t* val_off, uint8_t* vals,
-                  uint64_t cap, uint64_t* total, hipStream_t s, const cb_filterset* set = nullptr,
-                  const TierList* tl = nullptr) {
-  if (!which || !val_off || (nt && !tables)) return fail(CB_EINVAL, "null argument");
-  cb::TierArgs ta;
-  int tier_dev = 0;
-  if (tl) {
-    if (int rc = tier_args(*tl, nt, true, &ta, &tier_dev)) return rc;
-    hits = nullptr;
-    hit_rows = nullptr;
-  }
-  if (set) {
-    if (nt > set->width) return fail(CB_EINVAL, "more tables than the set's slots");
-    if (hit_rows)
+// ---- get_many_impl's steps, in the order it takes them ----
+
+// 1: the arguments and, for an enqueue-only call, where they live. ta /
+// gate_dev: a tiered gate's kernel argument and its sets' device.
+int check_get_args(const cb_table* const* tables, uint32_t nt, const Gate& g, const uint8_t* keys,
+                   const uint64_t* offsets, uint64_t n, const GetOut& o, cb::TierArgs* ta, int* gate_dev) {
+  if (!o.which || !o.val_off || (nt && !tables)) return fail(CB_EINVAL, "null argument");
+  if (g.kind == Gate::TIERS)
+    if (int rc = tier_args(*g.tiers, nt, true, ta, gate_dev)) return rc;
+  if (g.kind == Gate::SET) {
+    if (nt > g.set->width) return fail(CB_EINVAL, "more tables than the set's slots");
+    if (g.rows)
       for (uint32_t i = 0; i < nt; ++i)
-        if (hit_rows[i] >= set->width) return fail(CB_EINVAL, "slot out of range");
-    hits = nullptr;
+        if (g.rows[i] >= g.set->width) return fail(CB_EINVAL, "slot out of range");
   }
-  // total == NULL: enqueue only (every buffer on the device; val_off[n] = the total)
-  const bool async = total == nullptr;
-  if (async && (!is_device_ptr(which) || !is_device_ptr(val_off) || (vals && !is_device_ptr(vals)) ||
-                (hits && !is_device_ptr(hits)) || (n && keys && !is_device_ptr(keys)) ||
-                (offsets && !is_device_ptr(offsets))))
+  if (o.async() && (!is_device_ptr(o.which) || !is_device_ptr(o.val_off) || (o.vals && !is_device_ptr(o.vals)) ||
+                    (g.hits && !is_device_ptr(g.hits)) || (n && keys && !is_device_ptr(keys)) ||
+                    (offsets && !is_device_ptr(offsets))))
     return fail(CB_EINVAL, "total may be NULL only when keys, hits and outputs are device memory");
-  if (total) *total = 0;
-  if (n == 0) {
-    const uint64_t z = 0;
-    if (async) {
-      HIP_TRY(hipMemsetAsync(val_off, 0, 8, s));
-      return CB_OK;
-    }
-    return put_bytes((uint8_t*)val_off, &z, 8);
+  return CB_OK;
+}
+
+// 2: no keys: val_off[0] = 0 and nothing else.
+int answer_no_keys(const GetOut& o, hipStream_t s) {
+  const uint64_t z = 0;
+  if (o.async()) {
+    HIP_TRY(hipMemsetAsync(o.val_off, 0, 8, s));
+    return CB_OK;
   }
-  if (int rc = null_keys(keys, offsets, key_len)) return rc;  // (here: ahead of the table checks)
-  if (nt == 0) return fail(CB_EINVAL, "no tables");
-  const int dev = tables[0] ? tables[0]->device : 0;
-  std::vector<cb::TableView> views(nt);
-  uint64_t nrows = nt;
+  return put_bytes((uint8_t*)o.val_off, &z, 8);
+}
+
+// 3: the tables as views (all on device dev, the caller's current device),
+// the gate's sets on the same device, then each table's key buckets.
+int tables_to_views(const cb_table* const* tables, uint32_t nt, int dev, const Gate& g, int gate_dev, hipStream_t s,
+                    std::vector<cb::TableView>& views) {
   for (uint32_t i = 0; i < nt; ++i) {
     if (!tables[i]) return fail(CB_EINVAL, "null table");
     if (tables[i]->device != dev) return fail(CB_EINVAL, "tables live on different devices");
     if (int rc = finalize_table(const_cast<cb_table*>(tables[i]))) return rc;
     views[i] = tables[i]->view();
   }
-  if (set && set->device != dev) return fail(CB_EINVAL, "set and tables live on different devices");
-  if (tl && tier_dev != dev) return fail(CB_EINVAL, "sets and tables live on different devices");
-  std::vector<uint32_t> rows;
-  if ((hits || set) && hit_rows) {
-    rows.assign(hit_rows, hit_rows + nt);
+  if (g.kind == Gate::SET && g.set->device != dev) return fail(CB_EINVAL, "set and tables live on different devices");
+  if (g.kind == Gate::TIERS && gate_dev != dev) return fail(CB_EINVAL, "sets and tables live on different devices");
+  for (uint32_t i = 0; i < nt; ++i)
+    if (int rc = table_buckets(const_cast<cb_table*>(tables[i]), s, &views[i])) return rc;
+  return CB_OK;
+}
+
+// 4: the keys as the kernels see them, the tables' rows / slots (empty:
+// identity) and, for the ROWS gate, the hit rows on the device.
+int stage_keys_and_rows(Workspace& ws, const Gate& g, uint32_t nt, const uint8_t* keys, const uint64_t* offsets,
+                        uint32_t key_len, uint64_t n, hipStream_t s, StagedKeys& sk, std::vector<uint32_t>& rows,
+                        const uint64_t** dhits) {
+  uint64_t nrows = nt;
+  if ((g.hits || g.kind == Gate::SET) && g.rows) {
+    rows.assign(g.rows, g.rows + nt);
     nrows = 0;
     for (uint32_t r : rows) nrows = std::max<uint64_t>(nrows, (uint64_t)r + 1);
   }
-  DeviceGuard dg(dev);
-  for (uint32_t i = 0; i < nt; ++i)
-    if (int rc = table_buckets(const_cast<cb_table*>(tables[i]), s, &views[i])) return rc;
-  Workspace& ws = workspace(dev, s);
-  std::lock_guard<std::mutex> lk(ws.mu);
-  StagedKeys sk;
-  int rc = stage_keys(ws, keys, offsets, key_len, n, s, sk);
-  if (rc) return rc;
-  const uint64_t hwords = (n + 63) / 64;
-  const uint64_t* dhits = hits;
-  if (hits && !is_device_ptr(hits)) {
-    HIP_TRY(ws.hits.reserve(nrows * hwords * 8, s));
-    HIP_TRY(hipMemcpyAsync(ws.hits.p, hits, nrows * hwords * 8, hipMemcpyHostToDevice, s));
-    dhits = (const uint64_t*)ws.hits.p;
+  if (int rc = stage_keys(ws, keys, offsets, key_len, n, s, sk)) return rc;
+  *dhits = g.hits;
+  if (g.hits && !is_device_ptr(g.hits)) {
+    const uint64_t hbytes = nrows * ((n + 63) / 64) * 8;
+    HIP_TRY(ws.hits.reserve(hbytes, s));
+    HIP_TRY(hipMemcpyAsync(ws.hits.p, g.hits, hbytes, hipMemcpyHostToDevice, s));
+    *dhits = (const uint64_t*)ws.hits.p;
   }
-  // views and rows: uploaded only when they differ from what the workspace
-  // holds (stream-ordered, so earlier launches have read the old ones)
-  const size_t vbytes = nt * sizeof(cb::TableView);
-  const uint8_t* vb = (const uint8_t*)views.data();
-  if (ws.t_views_host.size() != vbytes || memcmp(ws.t_views_host.data(), vb, vbytes)) {
-    HIP_TRY(ws.t_views.reserve(vbytes, s));
-    HIP_TRY(hipMemcpyAsync(ws.t_views.p, vb, vbytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipStreamSynchronize(s));  // the source is pageable
-    ws.t_views_host.assign(vb, vb + vbytes);
-  }
-  const uint32_t* drows = nullptr;
+  return CB_OK;
+}
+
+// 5: views and rows to the device (when they changed), the answers' buffers
+// and the tail's scratch.
+int upload_tables(Workspace& ws, const std::vector<cb::TableView>& views, const std::vector<uint32_t>& rows,
+                  const GetOut& o, uint64_t n, hipStream_t s, GetBufs* b) {
+  if (int rc = upload_if_changed(ws.t_views, ws.t_views_host, views.data(), views.size() * sizeof(cb::TableView), s))
+    return rc;
+  b->views = (const cb::TableView*)ws.t_views.p;
+  b->rows = nullptr;
   if (!rows.empty()) {
-    if (ws.t_rows_host != rows) {
-      HIP_TRY(ws.t_rows.reserve(nt * 4, s));
-      HIP_TRY(hipMemcpyAsync(ws.t_rows.p, rows.data(), nt * 4, hipMemcpyHostToDevice, s));
-      HIP_TRY(hipStreamSynchronize(s));
-      ws.t_rows_host = rows;
-    }
-    drows = (const uint32_t*)ws.t_rows.p;
+    if (int rc = upload_if_changed(ws.t_rows, ws.t_rows_host, rows.data(), rows.size() * 4, s)) return rc;
+    b->rows = (const uint32_t*)ws.t_rows.p;
   }
-  int32_t* dwhich;
-  uint64_t* dvoff;
-  if ((rc = out_buf(ws.t_which, which, n, s, &dwhich))) return rc;
-  if ((rc = out_buf(ws.t_voff, val_off, n + 1, s, &dvoff))) return rc;
+  if (int rc = out_buf(ws.t_which, o.which, n, s, &b->which)) return rc;
+  if (int rc = out_buf(ws.t_voff, o.val_off, n + 1, s, &b->voff)) return rc;
   HIP_TRY(ws.t_line.reserve(n * 8, s));
   HIP_TRY(ws.t_dlen.reserve(n * 8, s));
   HIP_TRY(ws.t_scan.reserve(cb::get_tiles(n) * 8, s));
-  const cb::TableView* dviews = (const cb::TableView*)ws.t_views.p;
-  const uint64_t* vsrc = (const uint64_t*)ws.t_line.p;
-  const uint64_t* dlen = (const uint64_t*)ws.t_dlen.p;
-  uint64_t* tsum = (uint64_t*)ws.t_scan.p;
-  if (set && set_is_wide(set)) {
-    // the groups of 64 tables (newest first) and how each maps to slots:
-    // ascending or descending runs take their candidate bits from one window
-    // of the rows (wideset.hpp WideGroup), anything else one bit per table
-    const uint32_t ng = (nt + 63) / 64;
-    std::vector<cb::WideGroup> groups(ng);
-    bool need_slots = false;
-    for (uint32_t g = 0; g < ng; ++g) {
-      const uint32_t t0 = 64 * g, gn = std::min<uint32_t>(64, nt - t0);
-      auto slot = [&](uint32_t i) { return rows.empty() ? t0 + i : rows[t0 + i]; };
-      bool asc = true, desc = true;
-      for (uint32_t i = 1; i < gn; ++i) {
-        asc = asc && slot(i) == slot(0) + i;
-        desc = desc && slot(i) + i == slot(0);
-      }
-      cb::WideGroup& gd = groups[g];
-      gd.gn = gn;
-      if (asc) {
-        gd.kind = 0;
-        gd.lo = slot(0);
-      } else if (desc) {
-        gd.kind = 1;
-        gd.lo = slot(gn - 1);
-      } else {
-        gd.kind = 2;
-        gd.lo = 0;
-        need_slots = true;
-      }
+  b->vsrc = (uint64_t*)ws.t_line.p;
+  b->dlen = (uint64_t*)ws.t_dlen.p;
+  b->tsum = (uint64_t*)ws.t_scan.p;
+  return CB_OK;
+}
+
+// 6: the gate's launch, one function per gate.
+
+int launch_rows_gate(const uint64_t* dhits, uint32_t nt, const StagedKeys& sk, uint64_t n, const GetBufs& b,
+                     hipStream_t s) {
+  HIP_TRY(cb::launch_get_many(sk.keyk, b.views, nt, dhits, b.rows, (n + 63) / 64, sk.ks, n, b.which, b.vsrc, b.dlen,
+                              b.tsum, s));
+  return CB_OK;
+}
+
+int launch_set_gate(const cb_filterset* set, uint32_t nt, const StagedKeys& sk, uint64_t n, const GetBufs& b,
+                    hipStream_t s) {
+  const cb::ZoneView zv = set_zone_view(set);
+  HIP_TRY(cb::launch_set_get_many(sk.keyk, set->mode, set->width, set->words, set->mp, set->zany ? &zv : nullptr,
+                                  b.views, nt, b.rows, sk.ks, n, b.which, b.vsrc, b.dlen, b.tsum, s));
+  return set->zany ? note_zone_read(set, s) : CB_OK;
+}
+
+int launch_tier_gate(const TierList& tl, const cb::TierArgs& ta, const StagedKeys& sk, uint64_t n, const GetBufs& b,
+                     hipStream_t s) {
+  HIP_TRY(cb::launch_tier_get_many(sk.keyk, ta, b.views, sk.ks, n, b.which, b.vsrc, b.dlen, b.tsum, s));
+  return note_tier_reads(tl, ta, s);
+}
+
+// The wide gate takes its groups, its screen and its copy of the maps with it.
+int launch_wide_gate(Workspace& ws, const cb_filterset* set, const cb_table* const* tables,
+                     const std::vector<cb::TableView>& views, const std::vector<uint32_t>& rows,
+                     const StagedKeys& sk, uint64_t n, const GetBufs& b, hipStream_t s) {
+  const uint32_t nt = (uint32_t)views.size();
+  // the groups of 64 tables (newest first) and how each maps to slots:
+  // ascending or descending runs take their candidate bits from one window
+  // of the rows (wideset.hpp WideGroup), anything else one bit per table
+  const uint32_t ng = (nt + 63) / 64;
+  std::vector<cb::WideGroup> groups(ng);
+  bool need_slots = false;
+  for (uint32_t g = 0; g < ng; ++g) {
+    const uint32_t t0 = 64 * g, gn = std::min<uint32_t>(64, nt - t0);
+    auto slot = [&](uint32_t i) { return rows.empty() ? t0 + i : rows[t0 + i]; };
+    bool asc = true, desc = true;
+    for (uint32_t i = 1; i < gn; ++i) {
+      asc = asc && slot(i) == slot(0) + i;
+      desc = desc && slot(i) + i == slot(0);
     }
-    const uint8_t* gb = (const uint8_t*)groups.data();
-    const size_t gbytes = ng * sizeof(cb::WideGroup);
-    if (ws.t_groups_host.size() != gbytes || memcmp(ws.t_groups_host.data(), gb, gbytes)) {
-      HIP_TRY(ws.t_groups.reserve(gbytes, s));
-      HIP_TRY(hipMemcpyAsync(ws.t_groups.p, gb, gbytes, hipMemcpyHostToDevice, s));
-      HIP_TRY(hipStreamSynchronize(s));  // the source is pageable
-      ws.t_groups_host.assign(gb, gb + gbytes);
+    cb::WideGroup& gd = groups[g];
+    gd.gn = gn;
+    if (asc) {
+      gd.kind = 0;
+      gd.lo = slot(0);
+    } else if (desc) {
+      gd.kind = 1;
+      gd.lo = slot(gn - 1);
+    } else {
+      gd.kind = 2;
+      gd.lo = 0;
+      need_slots = true;
     }
-    const cb::WideZone wz = wide_zone_view(set);
-    cb::WideScreen scr{nullptr, 0, 0, 0};
-    if ((rc = wide_screen(ws, tables, views, rows, set->R, dviews, drows, s, &scr))) return rc;
-    // the tables' DirMaps in one contiguous array (gathered on the device
-    // when the table list changes: the walk stages a group's maps in the same
-    // pass as its views)
-    std::vector<uint64_t> msig;
-    msig.reserve(2 * (size_t)nt);
-    for (uint32_t i = 0; i < nt; ++i) {
-      msig.push_back(tables[i]->uid);
-      msig.push_back((uint64_t)(uintptr_t)views[i].dmap);
-    }
-    if (msig != ws.t_maps_sig) {
-      HIP_TRY(ws.t_maps.reserve((size_t)nt * sizeof(cb::DirMap), s));
-      HIP_TRY(cb::launch_gather_maps(dviews, nt, (cb::DirMap*)ws.t_maps.p, s));
-      ws.t_maps_sig.swap(msig);
-    }
-    const cb::DirMap* dmaps = (const cb::DirMap*)ws.t_maps.p;
-    // the A/B: maps found through the views (the round-5 staging)
-    static const bool no_maps = cb::knob_int("CB_WIDE_MAPS", 1) == 0;
-    if (no_maps) dmaps = nullptr;
-    HIP_TRY(cb::launch_wide_get_many(sk.keyk, set->mode, set->R, (const uint64_t*)set->words, set->mp,
-                                     set->zany ? &wz : nullptr, dviews, nt, (const cb::WideGroup*)ws.t_groups.p,
-                                     need_slots ? drows : nullptr, sk.ks, n, dwhich, (uint64_t*)ws.t_line.p,
-                                     (uint64_t*)ws.t_dlen.p, tsum, s, scr.scr ? &scr : nullptr, dmaps));
-    if (set->zany && (rc = note_zone_read(set, s))) return rc;
-  } else if (set) {
-    const cb::ZoneView zv = set_zone_view(set);
-    HIP_TRY(cb::launch_set_get_many(sk.keyk, set->mode, set->width, set->words, set->mp,
-                                    set->zany ? &zv : nullptr, dviews, nt, drows, sk.ks, n, dwhich,
-                                    (uint64_t*)ws.t_line.p, (uint64_t*)ws.t_dlen.p, tsum, s));
-    if (set->zany && (rc = note_zone_read(set, s))) return rc;
-  } else if (tl) {
-    HIP_TRY(cb::launch_tier_get_many(sk.keyk, ta, dviews, sk.ks, n, dwhich, (uint64_t*)ws.t_line.p,
-                                     (uint64_t*)ws.t_dlen.p, tsum, s));
-    if ((rc = note_tier_reads(*tl, ta, s))) return rc;
-  } else {
-    HIP_TRY(cb::launch_get_many(sk.keyk, dviews, nt, dhits, drows, hwords, sk.ks, n, dwhich,
-                                (uint64_t*)ws.t_line.p, (uint64_t*)ws.t_dlen.p, tsum, s));
   }
+  if (int rc = upload_if_changed(ws.t_groups, ws.t_groups_host, groups.data(), ng * sizeof(cb::WideGroup), s))
+    return rc;
+  const cb::WideZone wz = wide_zone_view(set);
+  cb::WideScreen scr{nullptr, 0, 0, 0};
+  if (int rc = wide_screen(ws, tables, views, rows, set->R, b.views, b.rows, s, &scr)) return rc;
+  // the tables' DirMaps in one contiguous array (gathered on the device
+  // when the table list changes: the walk stages a group's maps in the same
+  // pass as its views)
+  std::vector<uint64_t> msig;
+  msig.reserve(2 * (size_t)nt);
+  for (uint32_t i = 0; i < nt; ++i) {
+    msig.push_back(tables[i]->uid);
+    msig.push_back((uint64_t)(uintptr_t)views[i].dmap);
+  }
+  if (int rc = rebuild_if_changed(ws.t_maps_sig, msig, [&]() -> int {
+        HIP_TRY(ws.t_maps.reserve((size_t)nt * sizeof(cb::DirMap), s));
+        HIP_TRY(cb::launch_gather_maps(b.views, nt, (cb::DirMap*)ws.t_maps.p, s));
+        return CB_OK;
+      }))
+    return rc;
+  const cb::DirMap* dmaps = (const cb::DirMap*)ws.t_maps.p;
+  // the A/B: maps found through the views (the round-5 staging)
+  static const bool no_maps = cb::knob_int("CB_WIDE_MAPS", 1) == 0;
+  if (no_maps) dmaps = nullptr;
+  HIP_TRY(cb::launch_wide_get_many(sk.keyk, set->mode, set->R, (const uint64_t*)set->words, set->mp,
+                                   set->zany ? &wz : nullptr, b.views, nt, (const cb::WideGroup*)ws.t_groups.p,
+                                   need_slots ? b.rows : nullptr, sk.ks, n, b.which, b.vsrc, b.dlen, b.tsum, s,
+                                   scr.scr ? &scr : nullptr, dmaps));
+  return set->zany ? note_zone_read(set, s) : CB_OK;
+}
+
+// 7: the value tail, the same after every gate: the found values' offsets
+// (the tile sums' scan), their decode, and the answers back to the host.
+int value_tail(Workspace& ws, const GetBufs& b, uint64_t n, const GetOut& o, hipStream_t s) {
   // batches of up to 256K keys: the decode scans the tile sums itself (one
   // launch fewer per batch); larger ones: the one-block scan between
   bool raw = n && n <= cb::decode_raw_max();  // (n = 0: the scan kernel writes voff[0] = 0)
   static const bool no_raw = cb::knob_int("CB_DECODE_RAW", 1) == 0;
   if (no_raw) raw = false;
-  if (!raw) HIP_TRY(cb::launch_tile_scan(tsum, cb::get_tiles(n), dvoff + n, s));
+  if (!raw) HIP_TRY(cb::launch_tile_scan(b.tsum, cb::get_tiles(n), b.voff + n, s));
   if (!ws.htot) HIP_TRY(hipHostMalloc((void**)&ws.htot, kHostScratch, hipHostMallocDefault));
-  if (async) {
-    HIP_TRY(cb::launch_b64_decode(vsrc, dlen, tsum, n, dvoff, vals, vals ? cap : 0, s, raw));
+  if (o.async()) {
+    HIP_TRY(cb::launch_b64_decode(b.vsrc, b.dlen, b.tsum, n, b.voff, o.vals, o.vals ? o.cap : 0, s, raw));
     return CB_OK;
   }
-  if (vals && is_device_ptr(vals)) {
+  if (o.vals && is_device_ptr(o.vals)) {
     // device values: offsets and values in one pass (the kernel skips the
     // value writes when the total exceeds cap): one host round trip
-    HIP_TRY(cb::launch_b64_decode(vsrc, dlen, tsum, n, dvoff, vals, cap, s, raw));
-    HIP_TRY(hipMemcpyAsync(ws.htot, dvoff + n, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(cb::launch_b64_decode(b.vsrc, b.dlen, b.tsum, n, b.voff, o.vals, o.cap, s, raw));
+    HIP_TRY(hipMemcpyAsync(ws.htot, b.voff + n, 8, hipMemcpyDeviceToHost, s));
   } else {
-    HIP_TRY(cb::launch_b64_decode(vsrc, dlen, tsum, n, dvoff, nullptr, 0, s, raw));  // offsets only
-    HIP_TRY(hipMemcpyAsync(ws.htot, dvoff + n, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(cb::launch_b64_decode(b.vsrc, b.dlen, b.tsum, n, b.voff, nullptr, 0, s, raw));  // offsets only
+    HIP_TRY(hipMemcpyAsync(ws.htot, b.voff + n, 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     const uint64_t tot = *ws.htot;
-    if (vals && cap >= tot && tot) {
+    if (o.vals && o.cap >= tot && tot) {
       uint8_t* dvals;
-      if ((rc = out_buf(ws.t_vals, vals, tot, s, &dvals))) return rc;
-      HIP_TRY(cb::launch_b64_decode(vsrc, dlen, tsum, n, dvoff, dvals, tot, s, raw));
-      HIP_TRY(hipMemcpyAsync(vals, dvals, tot, hipMemcpyDeviceToHost, s));
+      if (int rc = out_buf(ws.t_vals, o.vals, tot, s, &dvals)) return rc;
+      HIP_TRY(cb::launch_b64_decode(b.vsrc, b.dlen, b.tsum, n, b.voff, dvals, tot, s, raw));
+      HIP_TRY(hipMemcpyAsync(o.vals, dvals, tot, hipMemcpyDeviceToHost, s));
     }
   }
-  if (dwhich != which) HIP_TRY(hipMemcpyAsync(which, dwhich, n * 4, hipMemcpyDeviceToHost, s));
-  if (dvoff != val_off) HIP_TRY(hipMemcpyAsync(val_off, dvoff, (n + 1) * 8, hipMemcpyDeviceToHost, s));
+  if (b.which != o.which) HIP_TRY(hipMemcpyAsync(o.which, b.which, n * 4, hipMemcpyDeviceToHost, s));
+  if (b.voff != o.val_off) HIP_TRY(hipMemcpyAsync(o.val_off, b.voff, (n + 1) * 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
-  *total = *ws.htot;
+  *o.total = *ws.htot;
   return CB_OK;
+}
+
+// Database::get for a batch of keys over tables[0..nt) (tables[0] newest),
+// the candidates chosen by gate g (cb_get_many_*, cb_set_get_many_*,
+// cb_tiers_get_many_*).
+int get_many_impl(const cb_table* const* tables, uint32_t nt, const Gate& g, const uint8_t* keys,
+                  const uint64_t* offsets, uint32_t key_len, uint64_t n, const GetOut& o, hipStream_t s) {
+  cb::TierArgs ta;
+  int gate_dev = 0;
+  if (int rc = check_get_args(tables, nt, g, keys, offsets, n, o, &ta, &gate_dev)) return rc;
+  if (o.total) *o.total = 0;
+  if (n == 0) return answer_no_keys(o, s);
+  if (int rc = null_keys(keys, offsets, key_len)) return rc;  // (here: ahead of the table checks)
+  if (nt == 0) return fail(CB_EINVAL, "no tables");
+  const int dev = tables[0] ? tables[0]->device : 0;
+  DeviceGuard dg(dev);
+  std::vector<cb::TableView> views(nt);
+  if (int rc = tables_to_views(tables, nt, dev, g, gate_dev, s, views)) return rc;
+  Workspace& ws = workspace(dev, s);
+  std::lock_guard<std::mutex> lk(ws.mu);
+  StagedKeys sk;
+  std::vector<uint32_t> rows;
+  const uint64_t* dhits;
+  if (int rc = stage_keys_and_rows(ws, g, nt, keys, offsets, key_len, n, s, sk, rows, &dhits)) return rc;
+  GetBufs b;
+  if (int rc = upload_tables(ws, views, rows, o, n, s, &b)) return rc;
+  int rc = CB_OK;
+  switch (g.kind) {
+    case Gate::ROWS: rc = launch_rows_gate(dhits, nt, sk, n, b, s); break;
+    case Gate::SET:
+      rc = set_is_wide(g.set) ? launch_wide_gate(ws, g.set, tables, views, rows, sk, n, b, s)
+                              : launch_set_gate(g.set, nt, sk, n, b, s);
+      break;
+    case Gate::TIERS: rc = launch_tier_gate(*g.tiers, ta, sk, n, b, s); break;
+  }
+  if (rc) return rc;
+  return value_tail(ws, b, n, o, s);
 }
 
 // The index of nl lines is one allocation: rec | pfx | fence | dir | dmap | llen.
@@ -1236,8 +1345,8 @@ int cb_get_many_fixed(const cb_table* const* tables, uint32_t nt, const uint64_t
                       const uint32_t* hit_rows, const uint8_t* keys, uint32_t key_len, uint64_t n,
                       int32_t* which, uint64_t* val_off, uint8_t* vals, uint64_t cap,
                       uint64_t* total, void* stream) {
-  return get_many_impl(tables, nt, hits, hit_rows, keys, nullptr, key_len, n, which, val_off, vals,
-                       cap, total, (hipStream_t)stream);
+  return get_many_impl(tables, nt, Gate::of_rows(hits, hit_rows), keys, nullptr, key_len, n,
+                       GetOut{which, val_off, vals, cap, total}, (hipStream_t)stream);
 }
 
 int cb_get_many_var(const cb_table* const* tables, uint32_t nt, const uint64_t* hits,
@@ -1245,8 +1354,8 @@ int cb_get_many_var(const cb_table* const* tables, uint32_t nt, const uint64_t* 
                     uint64_t n, int32_t* which, uint64_t* val_off, uint8_t* vals, uint64_t cap,
                     uint64_t* total, void* stream) {
   if (!offsets) return fail(CB_EINVAL, "null offsets");
-  return get_many_impl(tables, nt, hits, hit_rows, bytes, offsets, 0, n, which, val_off, vals, cap,
-                       total, (hipStream_t)stream);
+  return get_many_impl(tables, nt, Gate::of_rows(hits, hit_rows), bytes, offsets, 0, n,
+                       GetOut{which, val_off, vals, cap, total}, (hipStream_t)stream);
 }
 
 int cb_set_get_many_fixed(const cb_filterset* set, const cb_table* const* tables, uint32_t nt,
@@ -1254,8 +1363,8 @@ int cb_set_get_many_fixed(const cb_filterset* set, const cb_table* const* tables
                           int32_t* which, uint64_t* val_off, uint8_t* vals, uint64_t cap, uint64_t* total,
                           void* stream) {
   if (!set) return fail(CB_EINVAL, "null set");
-  return get_many_impl(tables, nt, nullptr, slots, keys, nullptr, key_len, n, which, val_off, vals, cap, total,
-                       (hipStream_t)stream, set);
+  return get_many_impl(tables, nt, Gate::of_set(set, slots), keys, nullptr, key_len, n,
+                       GetOut{which, val_off, vals, cap, total}, (hipStream_t)stream);
 }
 
 int cb_set_get_many_var(const cb_filterset* set, const cb_table* const* tables, uint32_t nt,
@@ -1264,8 +1373,8 @@ int cb_set_get_many_var(const cb_filterset* set, const cb_table* const* tables, 
                         void* stream) {
   if (!set) return fail(CB_EINVAL, "null set");
   if (!offsets) return fail(CB_EINVAL, "null offsets");
-  return get_many_impl(tables, nt, nullptr, slots, bytes, offsets, 0, n, which, val_off, vals, cap, total,
-                       (hipStream_t)stream, set);
+  return get_many_impl(tables, nt, Gate::of_set(set, slots), bytes, offsets, 0, n,
+                       GetOut{which, val_off, vals, cap, total}, (hipStream_t)stream);
 }
 
 int cb_tiers_get_many_fixed(const cb_filterset* const* sets, uint32_t ns, const cb_table* const* tables,
@@ -1273,8 +1382,8 @@ int cb_tiers_get_many_fixed(const cb_filterset* const* sets, uint32_t ns, const 
                             uint32_t key_len, uint64_t n, int32_t* which, uint64_t* val_off, uint8_t* vals,
                             uint64_t cap, uint64_t* total, void* stream) {
   const TierList tl{sets, ns, tiers, slots};
-  return get_many_impl(tables, nt, nullptr, nullptr, keys, nullptr, key_len, n, which, val_off, vals, cap, total,
-                       (hipStream_t)stream, nullptr, &tl);
+  return get_many_impl(tables, nt, Gate::of_tiers(&tl), keys, nullptr, key_len, n,
+                       GetOut{which, val_off, vals, cap, total}, (hipStream_t)stream);
 }
 
 int cb_tiers_get_many_var(const cb_filterset* const* sets, uint32_t ns, const cb_table* const* tables, uint32_t nt,
@@ -1283,8 +1392,8 @@ int cb_tiers_get_many_var(const cb_filterset* const* sets, uint32_t ns, const cb
                           uint64_t cap, uint64_t* total, void* stream) {
   if (!offsets) return fail(CB_EINVAL, "null offsets");
   const TierList tl{sets, ns, tiers, slots};
-  return get_many_impl(tables, nt, nullptr, nullptr, bytes, offsets, 0, n, which, val_off, vals, cap, total,
-                       (hipStream_t)stream, nullptr, &tl);
+  return get_many_impl(tables, nt, Gate::of_tiers(&tl), bytes, offsets, 0, n,
+                       GetOut{which, val_off, vals, cap, total}, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -26,6 +26,7 @@
 
 #include "blockscan.hpp"
 #include "compact.hpp"
+#include "launch.hpp"
 #include "profile.hpp"
 #include "zone.hpp"
 
@@ -199,14 +200,12 @@ __global__ __launch_bounds__(kNT) void k_compact_format(const SortKey* __restric
   if (tail0 + threadIdx.x < tl) g[tail0 + threadIdx.x] = (uint8_t)byte_at(line_of(tail0 + threadIdx.x), tail0 + threadIdx.x);
 }
 
-inline uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + kNT - 1) / kNT); }
-
 }  // namespace
 
 hipError_t launch_compact_klen(const CompactSrc* src, uint32_t nsrc, uint64_t n, uint64_t* klen, hipStream_t s) {
   if (!n) return hipSuccess;
   ProfScope ps("k_compact_klen", s);
-  hipLaunchKernelGGL(k_compact_klen, dim3(blocks_for(n)), dim3(kNT), 0, s, src, nsrc, n, klen);
+  hipLaunchKernelGGL(k_compact_klen, dim3(blocks_for(n, kNT)), dim3(kNT), 0, s, src, nsrc, n, klen);
   return hipGetLastError();
 }
 
@@ -214,7 +213,7 @@ hipError_t launch_compact_gather(const CompactSrc* src, uint32_t nsrc, uint64_t 
                                  CompactSide* side, uint64_t* dmask, hipStream_t s) {
   if (!n) return hipSuccess;
   ProfScope ps("k_compact_gather", s);
-  hipLaunchKernelGGL(k_compact_gather, dim3(blocks_for(n)), dim3(kNT), 0, s, src, nsrc, n, ko, kb, side, dmask);
+  hipLaunchKernelGGL(k_compact_gather, dim3(blocks_for(n, kNT)), dim3(kNT), 0, s, src, nsrc, n, ko, kb, side, dmask);
   return hipGetLastError();
 }
 
@@ -223,7 +222,7 @@ hipError_t launch_compact_select(const SortKey* order, const CompactSide* side, 
                                  hipStream_t s) {
   if (!n) return hipSuccess;
   ProfScope ps("k_compact_select", s);
-  hipLaunchKernelGGL(k_compact_select, dim3(blocks_for(n)), dim3(kNT), 0, s, order, side, kb, ko, n, slen, tcnt,
+  hipLaunchKernelGGL(k_compact_select, dim3(blocks_for(n, kNT)), dim3(kNT), 0, s, order, side, kb, ko, n, slen, tcnt,
                      tbytes, tkeys);
   return hipGetLastError();
 }
@@ -235,8 +234,8 @@ hipError_t launch_compact_format(const SortKey* order, const CompactSide* side, 
                                  hipStream_t s) {
   if (!n) return hipSuccess;
   ProfScope ps("k_compact_format", s);
-  hipLaunchKernelGGL(k_compact_format, dim3(blocks_for(n)), dim3(kNT), 0, s, order, side, slen, tcnt, tbytes, tkeys,
-                     totals, n, nl, out, rec, pfx, fence, llen, kb2, ko2);
+  hipLaunchKernelGGL(k_compact_format, dim3(blocks_for(n, kNT)), dim3(kNT), 0, s, order, side, slen, tcnt, tbytes,
+                     tkeys, totals, n, nl, out, rec, pfx, fence, llen, kb2, ko2);
   return hipGetLastError();
 }
 

@@ -14,6 +14,7 @@
 
 #include "blockscan.hpp"
 #include "flush.hpp"
+#include "launch.hpp"
 #include "profile.hpp"
 #include "zone.hpp"
 
@@ -21,8 +22,6 @@ namespace cb {
 namespace {
 
 constexpr uint32_t kNT = 256;  // = kFormatTile
-
-inline uint32_t blocks_for(uint64_t n, uint32_t per) { return (uint32_t)((n + per - 1) / per); }
 
 // The first 16 bytes of key p (output order) as zero-padded big-endian words,
 // and its length. Unsorted input: the sort record already holds them; sorted

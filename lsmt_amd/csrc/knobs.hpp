@@ -40,8 +40,8 @@
 //   CB_DENSE_HST          densefs.hip: 0 the zeroed hit words stored plain
 //   CB_DENSE_X            densefs.hip: k_dense_probe timing-only variant (wrong
 //                         hits): bit 0 skips the set[b] gathers, bit 1 the hit atomics
-//   CB_WIDE_SCREEN_BATCH  sstable.hip: summary words loaded together in the wide walk
-//   CB_WIDE_THREADS       sstable.hip: k_wide_get_many's workgroup size
+//   CB_WIDE_SCREEN_BATCH  getmany.hip: summary words loaded together in the wide walk
+//   CB_WIDE_THREADS       getmany.hip: k_wide_get_many's workgroup size
 #pragma once
 #include <cstdlib>
 

@@ -363,7 +363,7 @@ __host__ __device__ inline uint64_t bkt_bytes(uint32_t bits) {
 hipError_t launch_table_buckets(const LineRec* rec, uint64_t nlines, uint64_t* bkt, uint32_t bits,
                                 hipStream_t s);
 
-// ---- line index build: count -> scan -> emit -> finish ----
+// ---- line index build (sstable.hip): count -> scan -> emit -> finish ----
 constexpr uint32_t kLineChunk = 4096;  // bytes per block (256 threads x 16 B)
 inline uint64_t line_blocks(uint64_t len) { return (len + kLineChunk - 1) / kLineChunk; }
 // cnt[b] = non-empty line starts in chunk b
@@ -407,11 +407,13 @@ hipError_t launch_rebuild_gather(const uint8_t* data, const LineRec* rec, uint64
                                  const uint64_t* has_scan, const uint64_t* len_scan, uint8_t* out,
                                  uint64_t* off, uint64_t* lmap, hipStream_t s);
 
-// ---- resolution ----
+// ---- one table's search (sstable.hip; the per-key search is tablesearch.hpp) ----
 // line[k] = SsTable::binary_search(key k) over one table, or -1.
 hipError_t launch_table_search(int keyk, const TableView& t, const KeySrc& ks, uint64_t n,
                                int64_t* line, hipStream_t s);
-// Database::get's walk over tv[0..nt) (tv[0] newest). Table t is asked only
+
+// ---- Database::get's walk (getmany.hip) ----
+// launch_get_many: the walk over tv[0..nt) (tv[0] newest). Table t is asked only
 // where hits (nullable, [rows][hwords]) has bit k of row rows[t] (rows
 // nullable = identity). which[k] = first t whose line decodes as base64,
 // else -1; vsrc[k] the device address of that value's base64 bytes; dlen[k]
@@ -469,6 +471,8 @@ hipError_t launch_get_many(int keyk, const TableView* tv, uint32_t nt, const uin
                            const uint32_t* rows, uint64_t hwords, const KeySrc& ks, uint64_t n,
                            int32_t* which, uint64_t* vsrc, uint64_t* dlen, uint64_t* tsum,
                            hipStream_t s);
+
+// ---- the value tail (b64decode.hip) ----
 // Tile sums -> their exclusive scan in place; *total_out = the sum (one
 // single-block kernel; producers leave one sum per tile, consumers read their
 // block's base in one load, so no full-length scan pass).

@@ -1,5 +1,5 @@
 // tiermask.hpp — one key's gate over tiered filter sets (device code shared
-// by the tier probe, tierset.hip, and the fused read path, sstable.hip).
+// by the tier probe, tierset.hip, and the fused read path, getmany.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,6 +1,6 @@
 // wideset.hip — wide bit-sliced filter sets (wideset.hpp): set maintenance
 // and the hit-row probe for more than 64 slots. The fused read path over a
-// wide set (Database::get in one launch) is k_wide_get_many in sstable.hip.
+// wide set (Database::get in one launch) is k_wide_get_many in getmany.hip.
 #include <hip/hip_runtime.h>
 
 #include "profile.hpp"

@@ -61,7 +61,7 @@ hipError_t launch_wide_probe(int keyk, int mode, uint32_t R, const uint64_t* set
                              uint64_t n, const ModP& mp, const WideZone* zones, uint64_t* hits, uint64_t hwords,
                              hipStream_t s);
 
-// ---- device helpers shared with the fused read path (sstable.hip) ----
+// ---- device helpers shared with the fused read path (getmany.hip) ----
 
 // Bits [lo, lo + 64) of a row (R words), zero past the row.
 // A window across two words takes them in one 16-byte load (rows are 8-byte

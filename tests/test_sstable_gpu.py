@@ -231,7 +231,7 @@ def test_get_many_batches_of_changing_size(gpu):
 
 
 def test_get_many_decode_scan_boundary(gpu):
-    """Batches at the edge of the decode's own tile-sum scan (sstable.hip
+    """Batches at the edge of the decode's own tile-sum scan (b64decode.hip
     k_b64_decode<RAW>: up to 256K keys, 1024 tiles; one key more takes the
     k_tile_scan launch), on device and host outputs, each equal to the
     oracle, and a value buffer one byte short left untouched with the total
@@ -816,3 +816,65 @@ def test_get_many_bucket_budget_and_cross_stream_waits(gpu):
 def base64_of(i):
     import base64
     return base64.b64encode(b"val%d" % i)
+
+
+def _walk_expect(dicts, look):
+    """Database::get as a plain Python walk over the tables' dicts (newest
+    first): which, the value offsets and the value bytes."""
+    which, lens, vals = [], [], []
+    for k in look:
+        t = next((i for i, d in enumerate(dicts) if k in d), -1)
+        v = dicts[t][k] if t >= 0 else b""
+        which.append(t)
+        lens.append(len(v))
+        vals.append(v)
+    voff = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
+    return np.asarray(which, np.int32), voff, b"".join(vals)
+
+
+def test_get_many_table_and_row_uploads_follow_the_call(gpu):
+    """The workspace keeps what it last uploaded (the tables' views, their
+    rows / slots) and uploads again only when a call's differ
+    (capi_sstable.cpp upload_if_changed): a stale copy would answer from the
+    wrong table or gate without any error. One stream, five calls in a row
+    through the hit-row form and through a width-32 FilterSet: list A, a list
+    B of the same length with one table replaced, A again, A with permuted
+    rows / slots, a list one table shorter. Three tables of 5 lines with
+    overlapping keys whose values name their table, 65 keys (one past a wave)
+    of which some are absent; every result is compared exactly with a plain
+    Python newest-first walk over the tables' dicts. Each step's filters sit
+    only in that step's slots, so a stale slot array reads empty slots."""
+    import base64
+    pool = [b"key-%012d" % i for i in range(40)]           # 16-byte keys; 10 .. 39 are in no table
+    members = [[0, 1, 2, 3, 4], [2, 3, 4, 5, 6], [4, 5, 6, 7, 8], [1, 3, 5, 7, 9]]
+    dicts = [{pool[i]: b"table %d holds " % t + pool[i][-2 - t:] for i in m} for t, m in enumerate(members)]
+    tables, filters = [], []
+    for d in dicts:
+        tables.append(gpu.Table(b"".join(k + b"\t" + base64.b64encode(d[k]) + b"\n" for k in sorted(d))))
+        f = gpu.BloomFilter(1024)
+        f.insert_batch(np.frombuffer(b"".join(sorted(d)), np.uint8).reshape(len(d), 16).copy())
+        filters.append(f)
+    order = np.random.default_rng(65).permutation(65)
+    look_keys = [pool[(3 * int(i)) % 40] for i in order]
+    look = np.frombuffer(b"".join(look_keys), np.uint8).reshape(65, 16).copy()
+    assert sum(k in dicts[0] or k in dicts[1] or k in dicts[2] for k in look_keys) not in (0, 65)
+    steps = [([0, 1, 2], [0, 1, 2]),      # list A
+             ([0, 3, 2], [0, 3, 2]),      # list B: the same length, one table replaced
+             ([0, 1, 2], [0, 1, 2]),      # A again
+             ([0, 1, 2], [9, 4, 20]),     # A, its rows / slots permuted
+             ([0, 1], [9, 4])]            # one table shorter
+    for fused in (False, True):
+        for ids, slots in steps:
+            s = gpu.FilterSet(1024, width=32)
+            for t, slot in zip(ids, slots):
+                s.assign(slot, filters[t])
+            tabs = [tables[t] for t in ids]
+            rows = np.asarray(slots, np.uint32)
+            if fused:
+                which, voff, vals = gpu.get_many(tabs, look, filterset=s, hit_rows=rows)
+            else:
+                which, voff, vals = gpu.get_many(tabs, look, hits=s.probe(look), hit_rows=rows)
+            ew, evoff, evals = _walk_expect([dicts[t] for t in ids], look_keys)
+            assert np.array_equal(np.asarray(which), ew), (fused, ids, slots)
+            assert np.array_equal(np.asarray(voff, dtype=np.uint64), evoff), (fused, ids, slots)
+            assert vals == evals, (fused, ids, slots)

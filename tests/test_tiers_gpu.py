@@ -395,3 +395,41 @@ def test_refusals(gpu, base16):
     both(c.sets, 3, tiers, None, c.nt)
     # and the same arguments are accepted once they are within the limits
     assert np.array_equal(gpu.probe_tiers(c.sets, c.tiers, c.slots, keys), c.oracle_gate(c.look[:n]))
+
+
+def test_tiers_get_many_follows_the_tier_list_between_calls(gpu):
+    """Two calls in a row on one stream over the same four tables and keys,
+    the second after two of the tables swapped the tier they name: the views
+    stay as the workspace holds them (nothing to upload) while the tier list
+    changes, and each answer must come from the call's own list. Two tiers
+    (m = 1024 and a non-power-of-two m); overlapping tables whose values name
+    their table; 65 keys, some absent. Every result is compared exactly with a
+    plain Python newest-first walk over the tables' dicts; each run's filters
+    sit only in that run's tier and slot."""
+    ms = [1024, 1_000_003]
+    pool = [b"tier-%011d" % i for i in range(40)]          # 16-byte keys; 14 .. 39 are in no table
+    members = [[0, 1, 2, 3, 4], [3, 4, 5, 6, 7], [6, 7, 8, 9, 10], [1, 5, 9, 12, 13]]
+    keys = [sorted(pool[i] for i in m) for m in members]
+    tables = [gpu.Table(table_file(ks, t)) for t, ks in enumerate(keys)]
+    dicts = [{k: b"%d:" % t + k[::-1] for k in ks} for t, ks in enumerate(keys)]
+    look = [pool[(7 * i) % 40] for i in range(65)]
+    which_e, lens, vals_e = [], [], []
+    for k in look:
+        t = next((i for i, d in enumerate(dicts) if k in d), -1)
+        v = dicts[t][k] if t >= 0 else b""
+        which_e.append(t)
+        lens.append(len(v))
+        vals_e.append(v)
+    voff_e = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
+    assert set(which_e) == {-1, 0, 1, 2, 3}
+    slots = [3, 5, 7, 2]
+    for tiers in ([0, 1, 0, 1], [1, 0, 0, 1]):             # tables 0 and 1 swap tiers
+        sets = [gpu.FilterSet(m, width=32) for m in ms]
+        for t in range(4):
+            b = gpu.BloomFilter(ms[tiers[t]])
+            b.insert_batch(batch(gpu, keys[t], "k16"))
+            sets[tiers[t]].assign(slots[t], b)
+        which, voff, vals = gpu.get_many_tiers(tables, sets, tiers, slots, batch(gpu, look, "k16"))
+        assert np.array_equal(np.asarray(which), np.asarray(which_e, np.int32)), tiers
+        assert np.array_equal(np.asarray(voff, dtype=np.uint64), voff_e), tiers
+        assert vals == b"".join(vals_e), tiers

@@ -2,7 +2,7 @@
 encodes must be bit-exact (src/sstable.rs:57-72, 133-153), at the sizes where
 the hand-written branches change.
 
-Read path (sstable.hip): k_b64_decode's one-wait path (1..18 bytes) and its
+Read path (b64decode.hip): k_b64_decode's one-wait path (1..18 bytes) and its
 8-chars-per-step loop, each into the 16 KiB LDS stage or, when a block's 256
 values exceed it, into direct byte stores; b64_len's verdict on values that
 STANDARD.decode rejects (Database::get then falls through to an older table);
@@ -24,11 +24,11 @@ from oracle import oracle
 
 ALPHABET = b"ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789+/"
 BAD_CHARS = b"=-_ \t\r\x00\x80\xff"  # each outside the STANDARD alphabet
-DECODE_STAGE = 16384              # sstable.hip kDecodeLds
+DECODE_STAGE = 16384              # b64decode.hip kDecodeLds
 FORMAT_STAGES = (16384, 32768)    # flush.hip kFormatLdsSmall / kFormatLdsLarge
 TILE = 256                        # lookups / lines per block
 INLINE_TILES = 64                 # flush.hpp kFormatInlineTiles
-SMALL_B64 = 18                    # sstable.hip kSmallB64Bytes
+SMALL_B64 = 18                    # b64decode.hip kSmallB64Bytes
 
 
 def rand_bytes(rng, n) -> bytes:

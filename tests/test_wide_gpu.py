@@ -229,3 +229,49 @@ def test_wide_get_many_348_tables(gpu, lsm300, mapping):
     ow, ovoff, ovals = _oracle_expect(d, [ages[p] for p in newest_first])
     assert np.array_equal(np.asarray(which), ow)
     assert np.array_equal(np.asarray(voff, dtype=np.uint64), ovoff) and vals == ovals
+
+
+def test_wide_get_many_groups_follow_the_slots(gpu):
+    """The wide walk's per-call host data (the groups of 64 tables and how
+    each maps to slots, the screen, the maps' copy) is kept in the workspace
+    and replaced only when a call's differs (capi_sstable.cpp
+    upload_if_changed / rebuild_if_changed): stale groups would read the
+    wrong slots' bits without any error. One stream, the same 65 tables (two
+    groups) of 3 lines four times in a row: slots ascending, descending,
+    scattered (the groups' kinds go 0 -> 1 -> 2), ascending again. 65 keys,
+    some absent; every result is compared exactly with a plain Python
+    newest-first walk over the tables' dicts. Each step's filters sit only in
+    that step's slots."""
+    import base64
+    nt = 65
+    pool = [b"wide-%011d" % i for i in range(160)]         # 16-byte keys; 132 .. 159 are in no table
+    dicts = [{pool[2 * t + j]: b"t%02d/" % t + pool[2 * t + j][-3:] * (1 + t % 3) for j in range(3)}
+             for t in range(nt)]                             # neighbours share a key: the newer one wins
+    tables, filters = [], []
+    for d in dicts:
+        tables.append(gpu.Table(b"".join(k + b"\t" + base64.b64encode(d[k]) + b"\n" for k in sorted(d))))
+        f = gpu.BloomFilter(1024)
+        f.insert_batch(np.frombuffer(b"".join(sorted(d)), np.uint8).reshape(len(d), 16).copy())
+        filters.append(f)
+    look_keys = [pool[(13 * i) % 160] for i in range(65)]
+    look = np.frombuffer(b"".join(look_keys), np.uint8).reshape(65, 16).copy()
+    which_e, lens, vals_e = [], [], []
+    for k in look_keys:                                      # the plain walk, newest (table 0) first
+        t = next((i for i, d in enumerate(dicts) if k in d), -1)
+        v = dicts[t][k] if t >= 0 else b""
+        which_e.append(t)
+        lens.append(len(v))
+        vals_e.append(v)
+    voff_e = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
+    assert 0 < sum(w >= 0 for w in which_e) < 65 and max(which_e) == 64  # both groups answer, some keys absent
+    asc = np.arange(nt, dtype=np.uint32)
+    scattered = np.random.default_rng(128).permutation(128)[:nt].astype(np.uint32)
+    for name, slots in [("ascending", asc), ("descending", asc[::-1].copy()), ("scattered", scattered),
+                        ("ascending again", asc)]:
+        s = gpu.FilterSet(1024, width=128)
+        for t in range(nt):
+            s.assign(int(slots[t]), filters[t])
+        which, voff, vals = gpu.get_many(tables, look, filterset=s, hit_rows=slots)
+        assert np.array_equal(np.asarray(which), np.asarray(which_e, np.int32)), name
+        assert np.array_equal(np.asarray(voff, dtype=np.uint64), voff_e), name
+        assert vals == b"".join(vals_e), name
