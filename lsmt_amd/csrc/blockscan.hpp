@@ -20,6 +20,35 @@ __device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t x) {
   return x;
 }
 
+// Exclusive scan of arr[0..len) in LDS by a whole NT-thread block; returns the
+// total. wsum: NT/64 words of LDS scratch. Contains barriers: all threads call.
+template <uint32_t NT>
+__device__ uint32_t block_exclusive_scan(uint32_t* arr, uint32_t len, uint32_t* wsum) {
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wid = tid >> 6;
+  const uint32_t per = (len + NT - 1) / NT;
+  const uint32_t beg = min(tid * per, len), end = min(beg + per, len);
+  uint32_t s = 0;
+  for (uint32_t i = beg; i < end; ++i) s += arr[i];
+  const uint32_t x = wave_inclusive_scan(s);
+  if (lane == 63) wsum[wid] = x;
+  __syncthreads();
+  uint32_t wpre = 0, total = 0;
+#pragma unroll
+  for (uint32_t w = 0; w < NT / 64; ++w) {
+    const uint32_t v = wsum[w];
+    wpre += (w < wid) ? v : 0u;
+    total += v;
+  }
+  uint32_t run = wpre + x - s;
+  for (uint32_t i = beg; i < end; ++i) {
+    const uint32_t v = arr[i];
+    arr[i] = run;
+    run += v;
+  }
+  __syncthreads();
+  return total;
+}
+
 // Exclusive scan of arr[0..len4) in LDS by wave 0 alone (the other waves wait
 // at the caller's next barrier): one barrier fewer than block_exclusive_scan
 // and no cross-wave partials. len4 is a multiple of 4 and arr 16-B aligned and

@@ -18,9 +18,9 @@ int g_path_override = 0;  // 0 auto, 1 direct, 2 tiled
 constexpr int PATH_DIRECT = 1, PATH_TILED = 2;
 
 uint64_t alloc_words_for(uint64_t m) {
-  // Pad to whole 2^18-bit tiles (the largest LDS tile) so tiled passes never
-  // read or write past the allocation; small filters pad to one 2^16-bit
-  // tile (the smallest probe tile).
+  // Pad to whole tiles of kTileAlignBits (the largest LDS tile, the build's)
+  // so tiled passes never read or write past the allocation; small filters
+  // pad to one tile of kSmallAlignBits (the smallest probe tile).
   const uint64_t align = m >= cb::kSmallAlignBits ? cb::kTileAlignBits : cb::kSmallAlignBits;
   const uint64_t bits = std::max<uint64_t>((m + align - 1) / align * align, align);
   return bits / 32;
@@ -32,6 +32,16 @@ hipError_t ensure_pad_zeroed(const cb_filter* cf, hipStream_t s) {
   if (f->needs_pad_zero.exchange(false) && f->nwords_alloc > nw)
     return hipMemsetAsync(f->words + nw, 0, (f->nwords_alloc - nw) * 4, s);
   return hipSuccess;
+}
+
+// Readies f's words for a tiled build on s. A fresh filter's build writes
+// every tile of [0, T * 2^tb): a pending clear is moot there, and only the
+// padding past them (tiles past ceil(m/32) may not all be rewritten) is
+// zeroed; any other filter gets its pending clear.
+hipError_t ready_for_tiled_build(cb_filter* f, hipStream_t s) {
+  if (!f->known_zero) return cbx::ensure_zeroed(f, s);
+  if (f->needs_zero.exchange(false)) f->needs_pad_zero.store(true);
+  return ensure_pad_zeroed(f, s);
 }
 
 // A new write mark (recorded with the system-scope release: the mirror's
@@ -135,16 +145,8 @@ int insert_locked(Workspace& ws, cb_filter* f, const uint8_t* keys, const uint64
     HIP_TRY(ensure_zeroed(f, s));
     HIP_TRY(cb::launch_insert_direct(sk.keyk, f->mode, f->words, sk.ks, n, f->mp, s));
   } else {
-    // a fresh tiled build writes every tile of [0, T * 2^tb): the words past
-    // it are padding that no insert ever sets, so a pending clear is moot.
-    if (f->known_zero) {
-      if (f->needs_zero.exchange(false)) f->needs_pad_zero.store(true);
-      HIP_TRY(ensure_pad_zeroed(f, s));  // tiles past ceil(m/32) may not all be rewritten
-    } else {
-      HIP_TRY(ensure_zeroed(f, s));
-    }
-    // chunks of at most 4096 partition blocks of the largest block size
-    const uint64_t chunk = 4096ull * 256 * 16;
+    HIP_TRY(ready_for_tiled_build(f, s));
+    const uint64_t chunk = cb::build_chunk_keys();
     for (uint64_t k0 = 0; k0 < n; k0 += chunk) {
       const uint64_t nk = std::min(chunk, n - k0);
       const TilePlan p = cb::plan_build(f->m, nk);
@@ -265,7 +267,7 @@ int probe_impl(const cb_filter* const* filters, uint32_t nf, const uint8_t* keys
         HIP_TRY(cb::launch_probe_direct(sk.keyk, f0->mode, fp, cnt, sk.ks, n, f0->mp, dhits, hwords, s));
       }
     } else {
-      const uint64_t chunk = 4096ull * 256 * 8;  // keys per partition pass (multiple of 64)
+      const uint64_t chunk = cb::probe_chunk_keys();  // keys per partition pass (multiple of 64)
       for (uint64_t k0 = 0; k0 < n; k0 += chunk) {
         const uint64_t nk = std::min(chunk, n - k0);
         const TilePlan p = cb::plan_probe(m, nk);
@@ -663,8 +665,7 @@ int cb_filter_insert_fixed_many(cb_filter* const* filters, uint32_t nf, const ui
     nmax = std::max(nmax, n[i]);
   }
   if (nmax == 0) return CB_OK;
-  const uint64_t chunk_limit = 4096ull * 256 * 16;
-  if (choose_build_path(f0->m, nmax) != PATH_TILED || nmax > chunk_limit) {
+  if (choose_build_path(f0->m, nmax) != PATH_TILED || nmax > cb::build_chunk_keys()) {
     for (uint32_t i = 0; i < nf; ++i) {  // per-filter builds (direct path or huge batches)
       int rc = insert_impl(filters[i], keys[i], nullptr, key_len, n[i], s);
       if (rc) return rc;
@@ -711,12 +712,7 @@ int cb_filter_insert_fixed_many(cb_filter* const* filters, uint32_t nf, const ui
     cb::BuildBatch bb{};
     for (uint32_t j = 0; j < nb; ++j) {
       cb_filter* f = filters[b0 + j];
-      if (f->known_zero) {
-        if (f->needs_zero.exchange(false)) f->needs_pad_zero.store(true);
-        HIP_TRY(ensure_pad_zeroed(f, s));
-      } else {
-        HIP_TRY(ensure_zeroed(f, s));
-      }
+      HIP_TRY(ready_for_tiled_build(f, s));
       bb.ks[j].bytes = dkeys[b0 + j];
       bb.ks[j].offsets = nullptr;
       bb.ks[j].key_len = key_len;

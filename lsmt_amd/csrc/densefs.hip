@@ -38,6 +38,7 @@
 #include <type_traits>
 
 #include "blockscan.hpp"
+#include "devutil.hpp"
 #include "filterset.hpp"
 #include "knobs.hpp"
 #include "profile.hpp"
@@ -87,15 +88,6 @@ constexpr size_t dense_part_lds_max() { return dense_part_lds(kDenseMaxRegions);
 // CB_DENSE_HST 0 the hit words plain.
 constexpr int kDenseSt = CB_DENSE_ST;
 constexpr bool kDenseHitsNt = CB_DENSE_HST;
-typedef uint32_t dense_u32x4 __attribute__((ext_vector_type(4)));
-typedef int dense_i32x4 __attribute__((ext_vector_type(4)));
-
-// XCD-aware region order (workgroups are dealt round-robin over the 8 XCDs):
-// XCD x takes regions [x R/8, (x+1) R/8) in order.
-__device__ __forceinline__ uint32_t xcd_region(uint32_t bid, uint32_t R) {
-  if (R & 7u) return bid;
-  return (bid & 7u) * (R >> 3) + (bid >> 3);
-}
 
 // Keys [k0 + blockIdx.x C, ...) of the chunk: positions, region bins, the
 // block's region-sorted entries and its column of the run-start table.
@@ -215,21 +207,14 @@ __global__ __launch_bounds__(kDenseNT, kDensePartWaves) void k_dense_part(KeySrc
   const uint32_t total = hist[R];
   uint2* out = ent + (uint64_t)b * C;
   const uint32_t n2 = total / 2;
+  const uint4* st4 = reinterpret_cast<const uint4*>(stage);
   if constexpr (kDenseSt == 1) {
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(out, 0, total * 8, 0x00020000);
-    for (uint32_t i = tid; i < n2; i += NT) {
-      const uint4 v = reinterpret_cast<const uint4*>(stage)[i];
-      const dense_i32x4 w = {(int)v.x, (int)v.y, (int)v.z, (int)v.w};
-      __builtin_amdgcn_raw_buffer_store_b128(w, rs, i * 16, 0, 16);
-    }
+    for (uint32_t i = tid; i < n2; i += NT) store16_wt(rs, i * 16, st4[i]);
   } else if constexpr (kDenseSt == 2) {
-    for (uint32_t i = tid; i < n2; i += NT) {
-      const uint4 v = reinterpret_cast<const uint4*>(stage)[i];
-      const dense_u32x4 w = {v.x, v.y, v.z, v.w};
-      __builtin_nontemporal_store(w, reinterpret_cast<dense_u32x4*>(out) + i);
-    }
+    for (uint32_t i = tid; i < n2; i += NT) store16_nt(reinterpret_cast<uint4*>(out) + i, st4[i]);
   } else {
-    for (uint32_t i = tid; i < n2; i += NT) reinterpret_cast<uint4*>(out)[i] = reinterpret_cast<const uint4*>(stage)[i];
+    for (uint32_t i = tid; i < n2; i += NT) reinterpret_cast<uint4*>(out)[i] = st4[i];
   }
   if (tid == 0 && (total & 1u)) out[total - 1] = stage[total - 1];
 }
@@ -292,7 +277,7 @@ __global__ __launch_bounds__(kDenseNT, 8) void k_dense_probe(const void* __restr
   // them are never written, whatever their set words hold
   const word_t usedm = used >= W ? ~(word_t)0 : (((word_t)1 << used) - 1);
   const uint32_t tid = threadIdx.x;
-  const uint32_t r = xcd_region(blockIdx.x, R);
+  const uint32_t r = xcd_order(blockIdx.x, R);  // XCD x takes regions [x R/8, (x+1) R/8) in order
   const uint64_t p0 = (uint64_t)r << rshift;
   // the region's words in flight (64 KiB: four 16-B loads per lane) with the
   // run table's two rows

@@ -1,24 +1,16 @@
-// kernels.hpp — host-side launchers for the gfx950 Bloom kernels.
+// kernels.hpp — host-side launchers for the gfx950 Bloom kernels: direct.hip,
+// tilebuild.hip, tileprobe.hip and boolcodec.hip. The plans the tiled launchers
+// take come from tileplan.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "hash.hpp"
+#include "tileplan.hpp"
 
 namespace cb {
 
-constexpr uint32_t kMaxFiltersPerLaunch = 64;  // filter pointers carried in kernargs
-constexpr uint32_t kFiltersPerGroup = 32;      // one uint32 result mask per key
-constexpr uint32_t kMaxTiles = 4096;           // LDS histogram bound in the partition pass
-constexpr uint32_t kMaxTileBits = 19;          // build: 64 KiB LDS tiles at most
-constexpr uint32_t kMaxBuildBlocks = 4096;     // partition blocks per build launch (host chunks keys)
-constexpr uint32_t kMinTileBits = 12;          // build: 512 B tiles at least
-constexpr uint32_t kMinProbeTileBits = 16;     // probe kernel instantiations: 2^16..2^18
-constexpr uint32_t kMaxProbeTileBits = 18;
-// Filter allocations are padded to whole tiles of the largest tile size a pass
-// may use, so no tiled pass reads or writes past the allocation.
-constexpr uint64_t kTileAlignBits = 1ull << kMaxTileBits;
-constexpr uint64_t kSmallAlignBits = 1ull << kMinProbeTileBits;
+constexpr uint32_t kMaxFiltersPerLaunch = 64;  // filter pointers carried in kernargs (kFiltersPerGroup to a group)
 
 struct FilterPtrs {
   const uint32_t* w[kMaxFiltersPerLaunch];
@@ -35,28 +27,6 @@ struct BuildBatch {
   uint64_t fresh;  // bit i: filter i is known all-zero
 };
 static_assert(sizeof(BuildBatch) <= 3072, "a launch's arguments stay within the 4 KiB kernarg limit");
-
-// Geometry of one tiled pass (build or probe) over filters of m bits.
-struct TilePlan {
-  uint32_t tb;    // log2(tile bits)
-  uint32_t T;     // number of tiles = ceil(m / 2^tb)
-  uint32_t kpt;   // keys per thread in the partition pass
-  uint32_t C;     // keys per partition block = threads * kpt
-  uint32_t nblk;  // partition blocks = ceil(n / C)
-  uint32_t sub;   // build only: 0, or log2 of the 2^16-bit sub-tiles per tile (16-bit entries)
-};
-
-// nb: filters built together in one launch pair (insert_fixed_many batches).
-TilePlan plan_build(uint64_t m, uint64_t n, uint32_t nb = 1);
-TilePlan plan_probe(uint64_t m, uint64_t n);
-bool plan_ok(const TilePlan& p);  // tile count fits the partition histogram
-
-// Workspace bytes a tiled pass needs.
-size_t build_seg_bytes(const TilePlan& p);
-size_t build_ent_bytes(const TilePlan& p);
-size_t probe_seg_bytes(const TilePlan& p);
-size_t probe_ent_bytes(const TilePlan& p);
-size_t probe_lkey_bytes(const TilePlan& p);
 
 hipError_t launch_insert_direct(int keyk, int mode, uint32_t* words, const KeySrc& ks, uint64_t n,
                                 const ModP& mp, hipStream_t s);

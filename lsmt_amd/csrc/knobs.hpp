@@ -23,14 +23,14 @@
 //   CB_DECODE_RAW=0     capi_sstable.cpp: always the k_tile_scan launch before the decode
 //   CB_BIN_T=t          capi_sstable.cpp: bin-sort group target (0: no bin sort)
 //   CB_ORDER_FENCE=1    comm.cpp: the order event with its system-scope fence
-//   CB_BUILD_TB=b       kernels.hip plan_build: tile bits
-//   CB_BUILD_KPT=k      kernels.hip plan_build: partition keys per thread (1, 2, 4)
-//   CB_BUILD_SUB=0|1    kernels.hip plan_build: never / always 16-bit sub-tile entries
-//   CB_PROBE_TB=b       kernels.hip plan_probe: tile bits
-//   CB_PROBE_KPT=k      kernels.hip plan_probe: partition keys per thread (4, 8)
+//   CB_BUILD_TB=b       tileplan.cpp plan_build: tile bits
+//   CB_BUILD_KPT=k      tileplan.cpp plan_build: partition keys per thread (1, 2, 4)
+//   CB_BUILD_SUB=0|1    tileplan.cpp plan_build: never / always 16-bit sub-tile entries
+//   CB_PROBE_TB=b       tileplan.cpp plan_probe: tile bits
+//   CB_PROBE_KPT=k      tileplan.cpp plan_probe: partition keys per thread (4, 8)
 //
 // Compile-time (-D of an experiment build; the defaults below are the product):
-//   CB_BUILD_STORES       kernels.hip: build store policy bits (1 write-through
+//   CB_BUILD_STORES       tilebuild.hip: build store policy bits (1 write-through
 //                         partition entries, 2 non-temporal tile write-back)
 //   CB_DENSE_KPT          densefs.hip: partition keys per thread and batch
 //   CB_DENSE_NB           densefs.hip: key batches per partition block

@@ -7,6 +7,7 @@
 #include <type_traits>
 
 #include "hash.hpp"
+#include "launch.hpp"
 #include "zone.hpp"
 
 namespace cb {
@@ -105,22 +106,8 @@ __device__ __forceinline__ uint64_t slot_words(word_t mask, uint32_t used, uint3
   return mine;
 }
 
-// Every (key kind, hash mode) instantiation, by runtime values: CALL runs
-// with KK / MM as constants (inside a function that returns hipError_t).
-#define CB_KEY_MODE_DISPATCH(keyk, mode, CALL)                                      \
-  switch ((keyk) * 3 + (mode)) {                                                    \
-    case 0: { constexpr int KK = KEY_FIXED16, MM = MOD_POW2_32; CALL; } break;      \
-    case 1: { constexpr int KK = KEY_FIXED16, MM = MOD_POW2_64; CALL; } break;      \
-    case 2: { constexpr int KK = KEY_FIXED16, MM = MOD_GENERIC; CALL; } break;      \
-    case 3: { constexpr int KK = KEY_FIXED, MM = MOD_POW2_32; CALL; } break;        \
-    case 4: { constexpr int KK = KEY_FIXED, MM = MOD_POW2_64; CALL; } break;        \
-    case 5: { constexpr int KK = KEY_FIXED, MM = MOD_GENERIC; CALL; } break;        \
-    case 6: { constexpr int KK = KEY_VAR, MM = MOD_POW2_32; CALL; } break;          \
-    case 7: { constexpr int KK = KEY_VAR, MM = MOD_POW2_64; CALL; } break;          \
-    case 8: { constexpr int KK = KEY_VAR, MM = MOD_GENERIC; CALL; } break;          \
-    default: return hipErrorInvalidValue;                                           \
-  }
-// ... and set width (WW = 64 for a width of 64, else 32).
+// Every (key kind, hash mode, set width) instantiation: CB_KEY_MODE_DISPATCH
+// (launch.hpp) and WW = 64 for a width of 64, else 32.
 #define CB_SET_DISPATCH(keyk, mode, width, CALL)                                   \
   CB_KEY_MODE_DISPATCH(                                                            \
       keyk, mode, if ((width) != 64) { constexpr int WW = 32; CALL; } else { constexpr int WW = 64; CALL; })

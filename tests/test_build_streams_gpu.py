@@ -92,7 +92,7 @@ def test_build_tile_block_balance(gpu, m, n):
 @pytest.mark.parametrize("m", [1 << 25, (1 << 25) + 12345, 3 << 23, 1 << 22, 1 << 26])
 def test_batched_long_run_builds(gpu, m):
     """Batched builds of long runs take 16-bit entries in 2^16-bit sub-tiles
-    (kernels.hip plan_build: C4's shape): 12 filters, ragged counts around
+    (tileplan.cpp plan_build: C4's shape): 12 filters, ragged counts around
     2^18 keys, one of them a few keys repeated 60K times (super-runs past the
     two waves a tile workgroup loads at once), one already holding bits (the
     tile loaded, not cleared), m a power of two or not. The m's take every

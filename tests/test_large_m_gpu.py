@@ -6,7 +6,8 @@ Reference semantics: BloomFilter::hashes / insert / may_contain
 (/root/reference/src/bloom.rs:26-51) for every table of Database::get's
 fan-out (src/lib.rs:129-134).
 
-What the shapes reach (lsmt_amd/csrc/kernels.hip, capi_filter.cpp, capi_set.cpp, densefs.hip):
+What the shapes reach (lsmt_amd/csrc/tileprobe.hip, tilebuild.hip, direct.hip, capi_filter.cpp, capi_set.cpp,
+densefs.hip):
   * k_tile_probe<8,4,2>, the 2^18-bit tile with the two-deep register ring
     (plan_probe picks it for m >= 2^27 and n <= m/64): P1, P2, P6, P7, P8;
   * k_tile_probe<8,2,4> (tb = 17) with generic m, ragged keys, a partial last
@@ -40,14 +41,16 @@ bits, 70 001 lookups) cannot reach it at the sizes that make the case (about
 13 pairs at 2^28, under 1 at 2^32): their check is the position set, and the
 CPU test asserts present hits only for them.
 
-Plan values in the comments come from plan_probe / plan_build; _plan_probe
-restates plan_probe and the CPU test asserts each comment's values.
+Plan values in the comments come from plan_probe / plan_build (tileplan.cpp);
+tests/tileplan_ref.py restates them and the CPU test asserts each comment's
+values against it (tests/test_tileplan_cpu.py asserts them against the C++).
 """
 import functools
 
 import numpy as np
 import pytest
 
+import tileplan_ref
 from lsmt_amd import workload
 from oracle import oracle
 
@@ -307,15 +310,9 @@ PROBE_CASES = [("P1", None), ("P2", None), ("P2_fixed7", None), ("P2_var", None)
 
 
 def _plan_probe(m, n):
-    """plan_probe (kernels.hip): (tb, T, kpt, partition blocks)."""
-    tb1 = (m // 512 if m > 512 else 1).bit_length() - 1
-    want = m * 4096 // n
-    tb2 = (want if want else 1).bit_length() - 1
-    tb = min(max(min(tb1, tb2), 16), 18)
-    while tb < 18 and -(-m // (1 << tb)) > 4096:  # fit_tiles
-        tb += 1
-    kpt = 8 if n >= 512 * 2048 else 4
-    return tb, -(-m // (1 << tb)), kpt, -(-n // (256 * kpt))
+    """plan_probe (tileplan.cpp) by its restatement: (tb, T, kpt, partition blocks)."""
+    p = tileplan_ref.plan_probe(m, n)
+    return p.tb, p.T, p.kpt, p.nblk
 
 
 # ---- the CPU test -----------------------------------------------------------------------

@@ -1,7 +1,8 @@
 // ubench_build.hip — where a build's time goes (2^20
-// 16-byte keys -> one 2^27-bit filter; or C4's launch pair of 32 filters). Compiles the library's kernels.hip in
-// this translation unit with CB_STAMPS, so the build kernels record
-// s_memrealtime (100 MHz) at their phase boundaries. Reports:
+// 16-byte keys -> one 2^27-bit filter; or C4's launch pair of 32 filters).
+// Compiles the library's tilebuild.hip and tileplan.cpp in this translation
+// unit with CB_STAMPS, so the build kernels record s_memrealtime (100 MHz) at
+// their phase boundaries. Reports:
 //   - back-to-back time per launch of an empty 1024-thread kernel of the
 //     same grid and LDS (the launch + drain floor),
 //   - the two-kernel build per step, each kernel alone back to back,
@@ -9,7 +10,8 @@
 //     workgroup start to last workgroup end) from the stamps.
 // Output: one JSON object. Diagnostic only; not part of the product.
 #define CB_STAMPS 1
-#include "../lsmt_amd/csrc/kernels.hip"
+#include "../lsmt_amd/csrc/tilebuild.hip"
+#include "../lsmt_amd/csrc/tileplan.cpp"
 
 #include <algorithm>
 #include <cstdio>
@@ -115,46 +117,14 @@ int main(int argc, char** argv) {
   printf("{\"shape\": \"%s\", \"plan\": {\"tb\": %u, \"T\": %u, \"kpt\": %u, \"C\": %u, \"nblk\": %u, \"nb\": %u, \"sub\": %u}, ",
          c4 ? "c4" : "c2", p.tb, p.T, p.kpt, p.C, p.nblk, nb, p.sub);
 
-  const size_t lds1 = ((size_t)((p.T + 4) & ~3u) + 4 + 2 * p.C) * 4;  // hist, discard word, stage
-  const size_t lds2 = (size_t)(1u << (p.tb - 5)) * 4;
+  const size_t lds1 = build_part_lds(p), lds2 = build_tile_lds(p);
   allow_lds(k_empty, lds2 > lds1 ? lds2 : lds1);
   const float e1 = per_launch_us([&] { hipLaunchKernelGGL(k_empty, dim3(p.nblk, nb), dim3(1024), lds1, 0, dummy); }, 50);
   const float e2 = per_launch_us([&] { hipLaunchKernelGGL(k_empty, dim3(p.T, nb), dim3(1024), lds2, 0, dummy); }, 50);
   const float full = per_launch_us([&] { CHECK(launch_build_batch(KEY_FIXED16, mode, bb, nb, mp, p, seg, ent, 0)); }, 50);
-  if (p.kpt != 4) {
-    fprintf(stderr, "plan kpt %u: this tool times the kpt = 4 partition kernel\n", p.kpt);
-    return 1;
-  }
-  if (p.sub && p.sub != 2) {
-    fprintf(stderr, "plan sub %u: this tool times sub = 0 or 2\n", p.sub);
-    return 1;
-  }
-  const size_t lds1s = (size_t)((((p.T << p.sub) + 4) & ~3u) + 4) * 4 + 2 * p.C * 2;
-  allow_lds(k_build_part<KEY_FIXED16, MOD_POW2_32, 4>, lds1);
-  allow_lds(k_build_part<KEY_FIXED16, MOD_POW2_32, 4, uint16_t>, lds1s);
-  allow_lds((k_build_tile_sub<8, 2, 2, 512>), lds2);
-  auto launch_part = [&] {  // launch_build_batch's partition
-    if (p.sub)
-      hipLaunchKernelGGL((k_build_part<KEY_FIXED16, MOD_POW2_32, 4, uint16_t>), dim3(p.nblk, nb), dim3(1024), lds1s, 0,
-                         bb, mp, 16u, p.T << p.sub, seg, ent);
-    else
-      hipLaunchKernelGGL((k_build_part<KEY_FIXED16, MOD_POW2_32, 4>), dim3(p.nblk, nb), dim3(1024), lds1, 0, bb, mp,
-                         p.tb, p.T, seg, ent);
-  };
-  const bool longruns = 2ull * p.C > 48ull * p.T;  // launch_build_batch's choice
-  auto launch_tile = [&] {
-    if (p.sub)
-      hipLaunchKernelGGL((k_build_tile_sub<8, 2, 2, 512>), dim3(p.T, nb), dim3(512), lds2, 0, bb, p.tb, p.T, seg,
-                         p.nblk, reinterpret_cast<const uint16_t*>(ent), 2 * p.C);
-    else if (longruns)
-      hipLaunchKernelGGL((k_build_tile<8, 2>), dim3(p.T, nb), dim3(1024), lds2, 0, bb, p.tb, p.T, seg, p.nblk, ent,
-                         2 * p.C);
-    else
-      hipLaunchKernelGGL((k_build_tile<16, 1>), dim3(p.T, nb), dim3(1024), lds2, 0, bb, p.tb, p.T, seg, p.nblk, ent,
-                         2 * p.C);
-  };
-  allow_lds(k_build_tile<8, 2>, lds2);
-  allow_lds(k_build_tile<16, 1>, lds2);
+  // launch_build_batch's two steps, each alone
+  auto launch_part = [&] { CHECK(build_partition(KEY_FIXED16, mode, bb, nb, mp, p, seg, ent, 0)); };
+  auto launch_tile = [&] { CHECK(build_tiles(bb, nb, p, seg, ent, 0)); };
   const float part = per_launch_us(launch_part, 50);
   const float tile = per_launch_us(launch_tile, 50);
   printf("\"empty_part_grid_us\": %.2f, \"empty_tile_grid_us\": %.2f, \"build_step_us\": %.2f, "
