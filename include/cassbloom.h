@@ -340,6 +340,71 @@ int cb_sstable_create_bounded(const uint8_t* keys, const uint64_t* key_off, uint
  * own stream (the output's size depends on the data), never for the device. */
 int cb_tables_compact(const cb_table* const* tables, uint32_t nt, uint64_t m_bits, void* stream,
                       cb_table** table_out, cb_filter** bloom_out /* nullable */);
+
+/* ---- range and prefix scans over tables ------------------------------------
+ * The reference scans its memtable alone (Database::scan / scan_ns,
+ * src/lib.rs:144-146, 178-186): rows drop out of every scan and count once
+ * their memtable is flushed, while get still finds them. The scan of the
+ * tables is therefore defined as compaction is, through the reference
+ * functions it must be indistinguishable from. With tables[0] the NEWEST
+ * (cb_get_many_*'s order), K the keys of all their lines and a byte range
+ * [lo, hi), the result is, sorted ascending by key bytes (Rust's str Ord),
+ *   { (k, Database::get(k)) : k in K, lo <= k, (no hi or k < hi),
+ *                             Database::get(k) is Some }
+ * with Database::get (src/lib.rs:128-134) taken over these tables alone: a
+ * key keeps the value of the newest table whose line for it decodes, a key
+ * whose value decodes nowhere is absent, and values are the decoded bytes.
+ * With limit > 0 only the first `limit` entries are returned, and `truncated`
+ * says whether more qualified (the whole range is still merged: the limit
+ * bounds the result, not the work). The full range (lo_len == 0, has_hi == 0,
+ * limit == 0) is entry for entry the lines of cb_tables_compact's file, with
+ * the values decoded.
+ * The scan covers the tables only: a store merges its memtable's own scan
+ * over the result, memtable entries overriding, as it does for get.
+ *
+ * lo / hi: host bytes of any content (a prefix's end need not be UTF-8).
+ * lo_len == 0: from the first key. has_hi == 0: unbounded above (hi is
+ * ignored and may be NULL). lo >= hi: an empty result, not an error.
+ * which[i] = the index into tables[] of the table that supplied entry i
+ * (cb_get_many_*'s meaning). The inputs are not modified, inputs still
+ * pending from cb_sstable_create are finalised first, and the result owns all
+ * its memory, so the inputs may be destroyed as soon as the call returns.
+ * The call waits for its own stream (the result's size depends on the data),
+ * never for the device. CB_EINVAL (nothing returned, *out = NULL): out NULL,
+ * nt == 0, a null entry, tables on different devices, an input with lines
+ * that is not well-formed (cb_table_well_formed), lo or hi NULL with a
+ * non-zero length, 2^32 or more lines inside the range in all. Tables
+ * without lines are legal anywhere in the list. */
+/* A scan's result lives in device memory behind an opaque handle. The handle
+ * is spelled `void*` in these prototypes (cb_scan below is a name for it in
+ * prose only): it is made by cb_tables_scan*, read by cb_scan_*, and freed by
+ * cb_scan_destroy, and nothing else may be passed where one is expected. */
+int cb_tables_scan(const cb_table* const* tables, uint32_t nt, const uint8_t* lo, uint64_t lo_len,
+                   const uint8_t* hi, uint64_t hi_len, int has_hi, uint64_t limit, void* stream, void** out /* cb_scan */);
+/* cb_tables_scan over [prefix, cb_key_prefix_end(prefix)): every key that
+ * starts with prefix. Database::scan_ns(ns) is the prefix ns + ":"; stripping
+ * it from the returned keys is the caller's (src/lib.rs:184). */
+int cb_tables_scan_prefix(const cb_table* const* tables, uint32_t nt, const uint8_t* prefix, uint64_t prefix_len,
+                          uint64_t limit, void* stream, void** out /* cb_scan */);
+/* Host only, no device: the exclusive upper bound of "starts with prefix",
+ * i.e. the prefix without its trailing 0xFF bytes and its last remaining byte
+ * incremented (*out_len <= len bytes into out). *has_end = 0, *out_len = 0
+ * when nothing remains (an empty prefix, or all 0xFF): unbounded above. */
+int cb_key_prefix_end(const uint8_t* prefix, uint64_t len, uint8_t* out /* len bytes */, uint64_t* out_len,
+                      int* has_end);
+/* Every output nullable. truncated: 1 only when limit > 0 and more than
+ * limit entries qualified. */
+int cb_scan_info(const void* r, uint64_t* count, uint64_t* key_bytes, uint64_t* val_bytes, int* truncated);
+/* The result's parts, copied to host or device memory (as cb_table_lines
+ * copies): entry i's key is keys[key_off[i] .. key_off[i + 1]), its value
+ * vals[val_off[i] .. val_off[i + 1]). Either pointer of a pair may be NULL to
+ * skip that part. Synchronous; may be called any number of times. */
+int cb_scan_keys(const void* r, uint64_t* key_off /* count+1 */, uint8_t* keys);
+int cb_scan_values(const void* r, uint64_t* val_off /* count+1 */, uint8_t* vals);
+int cb_scan_which(const void* r, int32_t* which /* count */);
+/* Retires the result's memory through the block pool, like every other
+ * handle: no device-wide synchronise. */
+int cb_scan_destroy(void* r);
 /* Finalise a table from cb_sstable_create*: wait for its work, take its
  * results; returns its deferred error, if any. Idempotent, thread-safe. */
 int cb_table_wait(const cb_table* t);

@@ -28,6 +28,9 @@ from .bloom import (  # noqa: E402
     probe_tiers,
     sstable_create,
     compact,
+    scan,
+    prefix_end,
+    ScanResult,
     zone_bounds,
     ZoneMap,
     hits_compress,
@@ -37,5 +40,5 @@ from .bloom import (  # noqa: E402
 
 __all__ = ["BloomFilter", "BloomProto", "DeviceKeys", "FilterSet", "insert_many", "KeyBatch", "device_count", "last_path",
            "probe", "set_dense", "set_path", "unpack_hits", "zone_bounds", "ZoneMap", "TableMeta", "Table", "get_many", "sstable_create",
-           "compact", "probe_tiers", "get_many_tiers", "hits_compress", "hits_expand", "hits_expand_set"]
+           "compact", "scan", "prefix_end", "ScanResult", "probe_tiers", "get_many_tiers", "hits_compress", "hits_expand", "hits_expand_set"]
 __version__ = "0.1.0"

@@ -151,6 +151,14 @@ def load():
         "cb_sstable_create": ([u8p, P, u8p, P, u64, u64, i32, P, pp, pp, pu64, pu64], i32),
         "cb_sstable_create_bounded": ([u8p, P, u64, u8p, P, u64, u64, u64, i32, P, pp, pp], i32),
         "cb_tables_compact": ([P, u32, u64, P, pp, pp], i32),
+        "cb_tables_scan": ([P, u32, u8p, u64, u8p, u64, i32, u64, P, pp], i32),
+        "cb_tables_scan_prefix": ([P, u32, u8p, u64, u64, P, pp], i32),
+        "cb_key_prefix_end": ([u8p, u64, u8p, pu64, ctypes.POINTER(i32)], i32),
+        "cb_scan_info": ([P, pu64, pu64, pu64, ctypes.POINTER(i32)], i32),
+        "cb_scan_keys": ([P, P, u8p], i32),
+        "cb_scan_values": ([P, P, u8p], i32),
+        "cb_scan_which": ([P, P], i32),
+        "cb_scan_destroy": ([P], i32),
         "cb_table_wait": ([P], i32),
         "cb_table_zone": ([P, i32, u8p, u64, pu64], i32),
         "cb_table_rebuild": ([P, u64, P, pp, pu64, pu64], i32),

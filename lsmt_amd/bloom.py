@@ -833,6 +833,127 @@ def compact(tables: Sequence[Table], m: int = 1024, stream=None):
     return table, bloom, zone
 
 
+def _key_bytes(k) -> bytes:
+    return k.encode() if isinstance(k, str) else bytes(k)
+
+
+def prefix_end(prefix) -> "bytes | None":
+    """The exclusive upper bound of "starts with prefix" in byte order
+    (cb_key_prefix_end, host only): the prefix without its trailing 0xFF
+    bytes, its last remaining byte incremented; None when nothing remains (an
+    empty prefix, or all 0xFF), i.e. unbounded above."""
+    p = _key_bytes(prefix)
+    out = ctypes.create_string_buffer(max(len(p), 1))
+    n, has = ctypes.c_uint64(), ctypes.c_int()
+    check(_L().cb_key_prefix_end(p, len(p), out, ctypes.byref(n), ctypes.byref(has)))
+    return out.raw[:n.value] if has.value else None
+
+
+class ScanResult:
+    """A scan's entries in device memory (cb_scan_*): sorted by key, each with
+    its decoded value and the index in the scanned table list of the table
+    that supplied it. Complete when scan() returns; the scanned tables may be
+    closed while it lives."""
+
+    def __init__(self, handle: int, device: int):
+        self._h = ctypes.c_void_p(handle)
+        self.device = device
+        n, kb, vb, tr = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_int()
+        check(_L().cb_scan_info(self._h, ctypes.byref(n), ctypes.byref(kb), ctypes.byref(vb), ctypes.byref(tr)))
+        self.count, self.key_bytes, self.val_bytes = int(n.value), int(kb.value), int(vb.value)
+        self.truncated = bool(tr.value)
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) and self._h.value:
+            _L().cb_scan_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self) -> int:
+        return self.count
+
+    def copy_keys(self, key_off=None, keys=None) -> None:
+        """key_off (uint64[count + 1]) and / or keys (uint8[key_bytes]) into
+        numpy arrays or device tensors."""
+        check(_L().cb_scan_keys(self._h, _ptr_of(key_off)[0], _ptr_of(keys)[0]))
+
+    def copy_values(self, val_off=None, vals=None) -> None:
+        check(_L().cb_scan_values(self._h, _ptr_of(val_off)[0], _ptr_of(vals)[0]))
+
+    def copy_which(self, which) -> None:
+        check(_L().cb_scan_which(self._h, _ptr_of(which)[0]))
+
+    def raw(self):
+        """(key_off uint64[count + 1], keys uint8[key_bytes], val_off
+        uint64[count + 1], vals uint8[val_bytes]) as numpy arrays."""
+        ko, vo = np.zeros(self.count + 1, np.uint64), np.zeros(self.count + 1, np.uint64)
+        kb, vb = np.zeros(max(self.key_bytes, 1), np.uint8), np.zeros(max(self.val_bytes, 1), np.uint8)
+        self.copy_keys(ko, kb)
+        self.copy_values(vo, vb)
+        return ko, kb[:self.key_bytes], vo, vb[:self.val_bytes]
+
+    @staticmethod
+    def _split(off, data) -> "list[bytes]":
+        raw, o = data.tobytes(), off.tolist()
+        return [raw[o[i]:o[i + 1]] for i in range(len(o) - 1)]
+
+    def keys(self) -> "list[bytes]":
+        ko = np.zeros(self.count + 1, np.uint64)
+        kb = np.zeros(max(self.key_bytes, 1), np.uint8)
+        self.copy_keys(ko, kb)
+        return self._split(ko, kb)
+
+    def values(self) -> "list[bytes]":
+        vo = np.zeros(self.count + 1, np.uint64)
+        vb = np.zeros(max(self.val_bytes, 1), np.uint8)
+        self.copy_values(vo, vb)
+        return self._split(vo, vb)
+
+    def which(self) -> np.ndarray:
+        w = np.zeros(max(self.count, 1), np.int32)
+        self.copy_which(w)
+        return w[:self.count]
+
+    def items(self) -> "list[tuple[bytes, bytes]]":
+        return list(zip(self.keys(), self.values()))
+
+
+def scan(tables: Sequence[Table], lo=b"", hi=None, prefix=None, limit: int = 0, stream=None) -> ScanResult:
+    """Every live entry of well-formed tables (tables[0] newest, as get_many
+    takes them) whose key lies in [lo, hi), or starts with prefix, merged on
+    the device (cb_tables_scan): sorted by key bytes, each key with the value
+    Database::get (src/lib.rs:128-134) returns for it over these tables — the
+    newest line whose value decodes; a key whose value decodes nowhere is
+    absent. hi=None: unbounded above. limit > 0: the first `limit` entries,
+    ScanResult.truncated saying whether more qualified. The reference's
+    Database::scan / scan_ns (src/lib.rs:144-146, 178-186) read the memtable
+    alone; a store merges that over this result, as it does for get.
+    scan_ns(ns) is prefix = ns + ":". The tables are not modified and may be
+    closed as soon as the call returns."""
+    if prefix is not None and (hi is not None or _key_bytes(lo)):
+        raise ValueError("prefix excludes lo and hi")
+    if not tables:
+        arr, dev = None, 0
+    else:
+        arr = ctypes.cast((ctypes.c_void_p * len(tables))(*[t._h.value for t in tables]), ctypes.c_void_p)
+        dev = tables[0].device
+    h = ctypes.c_void_p()
+    if prefix is not None:
+        p = _key_bytes(prefix)
+        _raise(_L().cb_tables_scan_prefix(arr, len(tables), p, len(p), int(limit), _stream(stream), ctypes.byref(h)))
+    else:
+        lo_b = _key_bytes(lo)
+        hi_b = _key_bytes(hi) if hi is not None else None
+        _raise(_L().cb_tables_scan(arr, len(tables), lo_b, len(lo_b), hi_b, len(hi_b) if hi_b is not None else 0,
+                                   int(hi_b is not None), int(limit), _stream(stream), ctypes.byref(h)))
+    return ScanResult(h.value, dev)
+
+
 def _to_var(b: KeyBatch) -> KeyBatch:
     keys = np.ascontiguousarray(b.keys)
     offs = (np.arange(0, b.key_len * (b.n + 1), b.key_len, dtype=np.uint64) if b.key_len

@@ -217,6 +217,20 @@ struct cb_table {
   }
 };
 
+// A scan's result (cb_tables_scan): one pool block holding key_off | val_off
+// | which | keys | vals, complete when the call returns. An empty result has
+// no block.
+struct cb_scan {
+  int device = 0;
+  uint64_t count = 0, key_bytes = 0, val_bytes = 0;
+  bool truncated = false;
+  void* block = nullptr;
+  size_t block_cap = 0;
+  uint64_t *key_off = nullptr, *val_off = nullptr;  // count + 1 entries each
+  int32_t* which = nullptr;                         // count
+  uint8_t *keys = nullptr, *vals = nullptr;
+};
+
 namespace cbx {
 
 using cb::FilterPtrs;

@@ -1,7 +1,8 @@
 // capi_sstable.cpp — the C ABI for SSTable data files in HBM (SURVEY.md §8f
 // rows 3 and 4): indexing an existing file (cb_table_create), SsTable::create
 // on the device (cb_sstable_create), the batched binary search and
-// Database::get's newest-first walk (cb_get_many_*).
+// Database::get's newest-first walk (cb_get_many_*), compaction
+// (cb_tables_compact) and range scans (cb_tables_scan).
 //
 // Reference: /root/reference/src/sstable.rs:51-179, src/lib.rs:125-136.
 #include <chrono>
@@ -12,6 +13,8 @@
 
 #include "capi_internal.hpp"
 #include "compact.hpp"
+#include "keyrange.hpp"
+#include "scan.hpp"
 
 using namespace cbx;
 
@@ -562,6 +565,95 @@ int enqueue_key_sort(const SortPlan& plan, const uint8_t* kb, const uint64_t* ko
   const auto& [binned, T, tmp_bytes] = plan;
   if (binned) HIP_TRY(cb::launch_bin_sort(kb, ko, n, T, order, tmp, s, vo, vsp, tsum, dr));
   HIP_TRY(cb::launch_entry_sort(order, (cb::SortKey*)tmp, n, kb, ko, s, vo, vsp, tsum, &dr->flags[binned ? 3 : 0]));
+  return CB_OK;
+}
+
+// A pool block that is scratch for one call: released stream-ordered when it
+// leaves scope, on every return path.
+struct TempBlock {
+  int dev;
+  void* p = nullptr;
+  size_t cap = 0;
+  ~TempBlock() { pool_release(dev, p, cap); }
+};
+
+// The newest-wins merge that cb_tables_compact and cb_tables_scan run over
+// their sources (compact.hpp): the lines' keys gathered into one batch, the
+// stable key sort, the select of each key's newest decodable line and the
+// scanned tile sums of the survivors. Its scratch is one pool block.
+struct Merge {
+  uint64_t n = 0, kbound = 0, tiles = 0;  // lines, a bound on their keys' bytes, select tiles
+  SortPlan plan{};
+  cb::CompactSrc* dsrc = nullptr;  // room for the caller's sources (nsrc_cap of them)
+  uint64_t *klen = nullptr, *ko = nullptr, *scan = nullptr;
+  uint8_t* kb = nullptr;
+  cb::CompactSide* side = nullptr;
+  cb::SortKey* order = nullptr;
+  uint8_t* sort = nullptr;
+  uint64_t *slen = nullptr, *tcnt = nullptr, *tbytes = nullptr, *tkeys = nullptr, *tot = nullptr;
+  cb::CreateResult* dr = nullptr;
+};
+int merge_alloc(int dev, uint32_t nsrc_cap, uint64_t n, uint64_t kbound, TempBlock& tmp, Merge* m) {
+  m->n = n;
+  m->kbound = kbound;
+  m->tiles = cb::compact_tiles(n);
+  m->plan = plan_key_sort(n);  // the order: sorted as cb_sstable_create sorts a batch
+  size_t at = 0;
+  auto take = [&](uint64_t bytes) {
+    const size_t o = at;
+    at += (size_t)((bytes + 15) & ~15ull);
+    return o;
+  };
+  const size_t o_src = take(nsrc_cap * sizeof(cb::CompactSrc)), o_klen = take(n * 8), o_ko = take((n + 1) * 8),
+               o_scan = take(cb::scan_tmp_words(n) * 8), o_kb = take(kbound + 16),
+               o_side = take(n * sizeof(cb::CompactSide)), o_order = take(n * sizeof(cb::SortKey)),
+               o_sort = take(m->plan.tmp_bytes), o_slen = take(n * 8), o_tcnt = take(m->tiles * 8),
+               o_tbytes = take(m->tiles * 8), o_tkeys = take(m->tiles * 8), o_tot = take(3 * 8),
+               o_res = take(sizeof(cb::CreateResult));
+  if (pool_alloc(dev, at, &tmp.p, &tmp.cap) != hipSuccess) {
+    tmp.p = nullptr;
+    return fail(CB_ENOMEM, "device allocation failed for a merge's scratch");
+  }
+  uint8_t* b = (uint8_t*)tmp.p;
+  m->dsrc = (cb::CompactSrc*)(b + o_src);
+  m->klen = (uint64_t*)(b + o_klen);
+  m->ko = (uint64_t*)(b + o_ko);
+  m->scan = (uint64_t*)(b + o_scan);
+  m->kb = b + o_kb;
+  m->side = (cb::CompactSide*)(b + o_side);
+  m->order = (cb::SortKey*)(b + o_order);
+  m->sort = b + o_sort;
+  m->slen = (uint64_t*)(b + o_slen);
+  m->tcnt = (uint64_t*)(b + o_tcnt);
+  m->tbytes = (uint64_t*)(b + o_tbytes);
+  m->tkeys = (uint64_t*)(b + o_tkeys);
+  m->tot = (uint64_t*)(b + o_tot);
+  m->dr = (cb::CreateResult*)(b + o_res);
+  return CB_OK;
+}
+// The merge of sources dsrc[0..nsrc) (device, m.n lines in all) on s, up to
+// the survivors' totals h = {lines, file bytes, key bytes}: read back (they
+// size the caller's output), the stream waited for, and checked against the
+// inputs' bounds before anything is sized from them.
+int enqueue_merge(const Merge& m, const cb::CompactSrc* dsrc, uint32_t nsrc, hipStream_t s, uint64_t (&h)[3]) {
+  const uint64_t n = m.n;
+  HIP_TRY(cb::launch_compact_klen(dsrc, nsrc, n, m.klen, s));
+  HIP_TRY(cb::launch_scan_u64(m.klen, m.ko, n, m.scan, s));
+  // the bin sort's inputs: an unsorted batch (flags[0]) and its prefix byte masks
+  HIP_TRY(hipMemsetAsync(m.dr, 0, cb::kCreateHead, s));
+  HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)&m.dr->flags[0], 1, 1, s));
+  HIP_TRY(cb::launch_compact_gather(dsrc, nsrc, n, m.ko, m.kb, m.side, &m.dr->dmask[0][0], s));
+  // the stable sort by key, input index last: a key's lines leave it
+  // adjacent, newest first
+  if (int rc = enqueue_key_sort(m.plan, m.kb, m.ko, n, m.order, m.sort, m.dr, s, nullptr, nullptr, nullptr)) return rc;
+  HIP_TRY(cb::launch_compact_select(m.order, m.side, m.kb, m.ko, n, m.slen, m.tcnt, m.tbytes, m.tkeys, s));
+  HIP_TRY(cb::launch_tile_scan(m.tcnt, m.tiles, m.tot + 0, s));
+  HIP_TRY(cb::launch_tile_scan(m.tbytes, m.tiles, m.tot + 1, s));
+  HIP_TRY(cb::launch_tile_scan(m.tkeys, m.tiles, m.tot + 2, s));
+  h[0] = h[1] = h[2] = 0;
+  HIP_TRY(hipMemcpyAsync(h, m.tot, sizeof h, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (h[0] > n || h[2] > m.kbound || h[1] > m.kbound + n) return fail(CB_EHIP, "merge: inconsistent totals");
   return CB_OK;
 }
 
@@ -1171,66 +1263,23 @@ int cb_tables_compact(const cb_table* const* tables, uint32_t nt, uint64_t m_bit
     if ((rc = cb_filter_create(m_bits, dev, &fp))) return rc;
     f.reset(fp);
   }
-  struct TempBlock {
-    int dev;
-    void* p = nullptr;
-    size_t cap = 0;
-    ~TempBlock() { pool_release(dev, p, cap); }
-  } tmp{dev}, keys{dev};
+  TempBlock tmp{dev}, keys{dev};
   uint64_t cnt = 0, len = 0, kbytes = 0;
   if (n) {
-    const uint64_t tiles = cb::compact_tiles(n);
-    const SortPlan plan = plan_key_sort(n);  // the order: sorted as cb_sstable_create sorts a batch
-    size_t at = 0;
-    auto take = [&](uint64_t bytes) {
-      const size_t o = at;
-      at += (size_t)((bytes + 15) & ~15ull);
-      return o;
-    };
-    const size_t o_src = take(srcs.size() * sizeof(cb::CompactSrc)), o_klen = take(n * 8),
-                 o_ko = take((n + 1) * 8), o_scan = take(cb::scan_tmp_words(n) * 8), o_kb = take(kbound + 16),
-                 o_side = take(n * sizeof(cb::CompactSide)), o_order = take(n * sizeof(cb::SortKey)),
-                 o_sort = take(plan.tmp_bytes),
-                 o_slen = take(n * 8), o_tcnt = take(tiles * 8), o_tbytes = take(tiles * 8),
-                 o_tkeys = take(tiles * 8), o_tot = take(3 * 8), o_res = take(sizeof(cb::CreateResult));
-    if (pool_alloc(dev, at, &tmp.p, &tmp.cap) != hipSuccess) {
-      tmp.p = nullptr;
-      return fail(CB_ENOMEM, "device allocation failed for a compaction's scratch");
-    }
-    uint8_t* b = (uint8_t*)tmp.p;
-    cb::CompactSrc* dsrc = (cb::CompactSrc*)(b + o_src);
-    uint64_t* klen = (uint64_t*)(b + o_klen);
-    uint64_t* ko = (uint64_t*)(b + o_ko);
-    uint8_t* kb = b + o_kb;
-    cb::CompactSide* side = (cb::CompactSide*)(b + o_side);
-    cb::SortKey* order = (cb::SortKey*)(b + o_order);
-    uint64_t* slen = (uint64_t*)(b + o_slen);
-    uint64_t *tcnt = (uint64_t*)(b + o_tcnt), *tbytes = (uint64_t*)(b + o_tbytes), *tkeys = (uint64_t*)(b + o_tkeys);
-    uint64_t* tot = (uint64_t*)(b + o_tot);
+    Merge mg;
+    if ((rc = merge_alloc(dev, (uint32_t)srcs.size(), n, kbound, tmp, &mg))) return rc;
     const uint32_t nsrc = (uint32_t)srcs.size();
-    HIP_TRY(hipMemcpyAsync(dsrc, srcs.data(), nsrc * sizeof(cb::CompactSrc), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(mg.dsrc, srcs.data(), nsrc * sizeof(cb::CompactSrc), hipMemcpyHostToDevice, s));
     HIP_TRY(hipStreamSynchronize(s));  // the source is pageable
-    HIP_TRY(cb::launch_compact_klen(dsrc, nsrc, n, klen, s));
-    HIP_TRY(cb::launch_scan_u64(klen, ko, n, (uint64_t*)(b + o_scan), s));
-    // the bin sort's inputs: an unsorted batch (flags[0]) and its prefix byte masks
-    cb::CreateResult* dr = (cb::CreateResult*)(b + o_res);
-    HIP_TRY(hipMemsetAsync(dr, 0, cb::kCreateHead, s));
-    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)&dr->flags[0], 1, 1, s));
-    HIP_TRY(cb::launch_compact_gather(dsrc, nsrc, n, ko, kb, side, &dr->dmask[0][0], s));
-    // the stable sort by key, input index last: a key's lines leave it
-    // adjacent, newest first
-    if ((rc = enqueue_key_sort(plan, kb, ko, n, order, b + o_sort, dr, s, nullptr, nullptr, nullptr))) return rc;
-    HIP_TRY(cb::launch_compact_select(order, side, kb, ko, n, slen, tcnt, tbytes, tkeys, s));
-    HIP_TRY(cb::launch_tile_scan(tcnt, tiles, tot + 0, s));
-    HIP_TRY(cb::launch_tile_scan(tbytes, tiles, tot + 1, s));
-    HIP_TRY(cb::launch_tile_scan(tkeys, tiles, tot + 2, s));
-    uint64_t h[3] = {0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(h, tot, sizeof h, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    uint64_t h[3];
+    if ((rc = enqueue_merge(mg, mg.dsrc, nsrc, s, h))) return rc;
     cnt = h[0];
     len = h[1];
     kbytes = h[2];
-    if (cnt > n || kbytes > kbound || len > kbound + n) return fail(CB_EHIP, "compaction: inconsistent totals");
+    cb::SortKey* order = mg.order;
+    cb::CompactSide* side = mg.side;
+    uint64_t *slen = mg.slen, *tcnt = mg.tcnt, *tbytes = mg.tbytes, *tkeys = mg.tkeys, *tot = mg.tot;
+    cb::CreateResult* dr = mg.dr;
     t->len = len;
     if ((rc = alloc_file(t.get(), len + 16))) return rc;
     HIP_TRY(hipMemsetAsync(t->data + len, 0, 16, s));
@@ -1276,6 +1325,256 @@ int cb_tables_compact(const cb_table* const* tables, uint32_t nt, uint64_t m_bit
   if (!cnt && (rc = finish_empty_file(t.get(), s))) return rc;
   if (bloom_out) *bloom_out = f.release();
   *table_out = t.release();
+  return CB_OK;
+}
+
+namespace {
+// A result's block: key_off | val_off | which | keys | vals, for count entries
+// and room for kb key bytes and vb value bytes.
+size_t scan_layout(uint64_t count, uint64_t kb, uint64_t vb, size_t (&o)[5]) {
+  size_t at = 0;
+  const uint64_t part[5] = {(count + 1) * 8, (count + 1) * 8, count * 4, kb + 16, vb + 16};
+  for (int i = 0; i < 5; ++i) {
+    o[i] = at;
+    at += (size_t)((part[i] + 15) & ~15ull);
+  }
+  return at;
+}
+size_t scan_bytes(uint64_t count, uint64_t kb, uint64_t vb) {
+  size_t o[5];
+  return scan_layout(count, kb, vb, o);
+}
+int scan_alloc(cb_scan* r, uint64_t count, uint64_t kb, uint64_t vb) {
+  size_t o[5];
+  const size_t bytes = scan_layout(count, kb, vb, o);
+  if (pool_alloc(r->device, bytes, &r->block, &r->block_cap) != hipSuccess) {
+    r->block = nullptr;
+    return fail(CB_ENOMEM, "device allocation failed for a scan's result");
+  }
+  uint8_t* b = (uint8_t*)r->block;
+  r->key_off = (uint64_t*)(b + o[0]);
+  r->val_off = (uint64_t*)(b + o[1]);
+  r->which = (int32_t*)(b + o[2]);
+  r->keys = b + o[3];
+  r->vals = b + o[4];
+  return CB_OK;
+}
+}  // namespace
+
+// Range scan (scan.hpp): the tables cut to [lo, hi) on the device, the cuts
+// merged as compaction merges whole tables, the survivors' keys and decoded
+// values written into the result. Scratch as in cb_tables_compact: pool blocks
+// released stream-ordered on every return path. The call waits for its own
+// stream after staging the table list (pageable memory) and then three times
+// for a few words, each bound-checked before anything is sized from it: the
+// cuts' totals (the merge's scratch), the survivors' totals (the result), and
+// the kept keys' and values' byte totals at the end (the result is complete
+// when the call returns). A limit's result is then copied into a block of its
+// own size, so what a caller keeps is sized by what it asked for.
+int cb_tables_scan(const cb_table* const* tables, uint32_t nt, const uint8_t* lo, uint64_t lo_len, const uint8_t* hi,
+                   uint64_t hi_len, int has_hi, uint64_t limit, void* stream, void** out) {
+  if (!out) return fail(CB_EINVAL, "null argument");
+  *out = nullptr;
+  if (!nt || !tables) return fail(CB_EINVAL, "no tables");
+  for (uint32_t i = 0; i < nt; ++i)
+    if (!tables[i]) return fail(CB_EINVAL, "null table");
+  const int dev = tables[0]->device;
+  for (uint32_t i = 0; i < nt; ++i)
+    if (tables[i]->device != dev) return fail(CB_EINVAL, "tables live on different devices");
+  if (lo_len && !lo) return fail(CB_EINVAL, "null lower bound with a length");
+  if (!has_hi) hi_len = 0;
+  if (hi_len && !hi) return fail(CB_EINVAL, "null upper bound with a length");
+  hipStream_t s = (hipStream_t)stream;
+  // the non-empty tables, newest first
+  std::vector<cb::ScanTable> tabs;
+  uint64_t all_lines = 0, all_bytes = 0;
+  for (uint32_t i = 0; i < nt; ++i) {
+    cb_table* ti = const_cast<cb_table*>(tables[i]);
+    if (int rc = finalize_table(ti)) return rc;
+    if (!ti->nlines) continue;
+    if (!ti->fast) return fail(CB_EINVAL, "an input table is not well-formed");
+    tabs.push_back(cb::ScanTable{ti->data, ti->rec, ti->pfx, ti->fence, ti->llen, ti->nlines, ti->len, i, 0});
+    all_lines += ti->nlines;
+    all_bytes += ti->len;
+  }
+  std::unique_ptr<cb_scan, int (*)(void*)> r(new cb_scan(), cb_scan_destroy);
+  r->device = dev;
+  // nothing to search: no lines at all, or lo >= hi
+  if (tabs.empty() || (has_hi && cb::key_cmp(lo, lo_len, hi, hi_len) >= 0)) {
+    *out = r.release();
+    return CB_OK;
+  }
+  int rc = cb_init(dev);
+  if (rc) return rc;
+  DeviceGuard dg(dev);
+  (void)workspace(dev, s);  // (registers s: the pool retires blocks behind it)
+  TempBlock cuts{dev}, tmp{dev}, vtmp{dev};
+  size_t at = 0;
+  auto take = [&](uint64_t bytes) {
+    const size_t o = at;
+    at += (size_t)((bytes + 15) & ~15ull);
+    return o;
+  };
+  // 1: every table's cut, and the cuts as the merge's sources
+  const uint32_t ntab = (uint32_t)tabs.size();
+  const size_t o_tab = take(ntab * sizeof(cb::ScanTable)), o_bnd = take(lo_len + hi_len + 16), up_bytes = at,
+               o_cut = take(ntab * sizeof(cb::ScanCut)), o_src = take(ntab * sizeof(cb::CompactSrc)),
+               o_map = take(ntab * 4), o_ctot = take(3 * 8);
+  if (pool_alloc(dev, at, &cuts.p, &cuts.cap) != hipSuccess) {
+    cuts.p = nullptr;
+    return fail(CB_ENOMEM, "device allocation failed for a scan's cuts");
+  }
+  uint8_t* cbase = (uint8_t*)cuts.p;
+  std::vector<uint8_t> up(up_bytes, 0);
+  std::memcpy(&up[o_tab], tabs.data(), ntab * sizeof(cb::ScanTable));
+  if (lo_len) std::memcpy(&up[o_bnd], lo, lo_len);
+  if (hi_len) std::memcpy(&up[o_bnd + lo_len], hi, hi_len);
+  HIP_TRY(hipMemcpyAsync(cbase, up.data(), up_bytes, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipStreamSynchronize(s));  // the source is pageable
+  const cb::ScanTable* dtab = (const cb::ScanTable*)(cbase + o_tab);
+  cb::ScanCut* dcut = (cb::ScanCut*)(cbase + o_cut);
+  cb::CompactSrc* dsrc = (cb::CompactSrc*)(cbase + o_src);
+  uint32_t* dmap = (uint32_t*)(cbase + o_map);
+  uint64_t* dctot = (uint64_t*)(cbase + o_ctot);
+  const cb::ScanRange range{cbase + o_bnd, lo_len, lo_len, hi_len, has_hi ? 1u : 0u, 0};
+  HIP_TRY(cb::launch_scan_bounds(dtab, ntab, range, dcut, s));
+  HIP_TRY(cb::launch_scan_sources(dtab, dcut, ntab, dsrc, dmap, dctot, s));
+  uint64_t c[3] = {0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(c, dctot, sizeof c, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  const uint64_t n = c[0], kbound = c[1], nsrc = c[2];
+  if (n > all_lines || kbound > all_bytes || nsrc > ntab || nsrc > n || (n && !nsrc))
+    return fail(CB_EHIP, "scan: inconsistent cut totals");
+  if (n > 0xFFFFFFFFull) return fail(CB_EINVAL, "too many lines inside the range for one scan");
+  if (!n) {
+    *out = r.release();
+    return CB_OK;
+  }
+  // 2: compaction's merge over the cuts
+  Merge mg;
+  if ((rc = merge_alloc(dev, 0, n, kbound, tmp, &mg))) return rc;
+  uint64_t h[3];
+  if ((rc = enqueue_merge(mg, dsrc, (uint32_t)nsrc, s, h))) return rc;
+  const uint64_t cnt = h[0], len = h[1], kbytes = h[2];
+  if (len < kbytes + 2 * cnt) return fail(CB_EHIP, "scan: inconsistent totals");
+  if (!cnt) {
+    *out = r.release();
+    return CB_OK;
+  }
+  // 3: the result. A kept line is `key \t text \n` and its value decodes to at
+  // most 3 bytes per 4 of text, which bounds the values before any is decoded.
+  const uint64_t count = limit && limit < cnt ? limit : cnt;
+  const uint64_t vcap = (len - kbytes - 2 * cnt) / 4 * 3;
+  if ((rc = scan_alloc(r.get(), count, kbytes, vcap))) return rc;
+  const uint64_t vtiles = cb::get_tiles(count);
+  at = 0;
+  const size_t o_vsrc = take(count * 8), o_dlen = take(count * 8), o_vsum = take(vtiles * 8);
+  if (pool_alloc(dev, at, &vtmp.p, &vtmp.cap) != hipSuccess) {
+    vtmp.p = nullptr;
+    return fail(CB_ENOMEM, "device allocation failed for a scan's value spans");
+  }
+  uint8_t* vb = (uint8_t*)vtmp.p;
+  uint64_t *vsrc = (uint64_t*)(vb + o_vsrc), *dlen = (uint64_t*)(vb + o_dlen), *vsum = (uint64_t*)(vb + o_vsum);
+  HIP_TRY(hipMemsetAsync(vsum, 0, vtiles * 8, s));
+  HIP_TRY(cb::launch_scan_emit(mg.order, mg.side, mg.slen, mg.tcnt, mg.tkeys, mg.tot, dsrc, dmap, (uint32_t)nsrc, n,
+                               count, r->keys, r->key_off, r->which, vsrc, dlen, vsum, s));
+  // the read path's value tail: small results scan the tile sums in the decode itself
+  const bool raw = count <= cb::decode_raw_max();
+  if (!raw) HIP_TRY(cb::launch_tile_scan(vsum, vtiles, r->val_off + count, s));
+  HIP_TRY(cb::launch_b64_decode(vsrc, dlen, vsum, count, r->val_off, r->vals, vcap, s, raw));
+  uint64_t e[2] = {0, 0};
+  HIP_TRY(hipMemcpyAsync(&e[0], r->key_off + count, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(&e[1], r->val_off + count, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (e[0] > kbytes || e[1] > vcap) return fail(CB_EHIP, "scan: inconsistent result totals");
+  r->count = count;
+  r->key_bytes = e[0];
+  r->val_bytes = e[1];
+  r->truncated = count < cnt;
+  // a limit's result was sized for the whole range: keep a block of its own size
+  if (r->truncated && scan_bytes(count, e[0], e[1]) * 2 < r->block_cap) {
+    cb_scan big = *r;
+    TempBlock old{dev, big.block, big.block_cap};
+    r->block = nullptr;
+    if ((rc = scan_alloc(r.get(), count, e[0], e[1]))) return rc;
+    HIP_TRY(hipMemcpyAsync(r->key_off, big.key_off, (count + 1) * 8, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(r->val_off, big.val_off, (count + 1) * 8, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(r->which, big.which, count * 4, hipMemcpyDeviceToDevice, s));
+    if (e[0]) HIP_TRY(hipMemcpyAsync(r->keys, big.keys, e[0], hipMemcpyDeviceToDevice, s));
+    if (e[1]) HIP_TRY(hipMemcpyAsync(r->vals, big.vals, e[1], hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
+  }
+  *out = r.release();
+  return CB_OK;
+}
+
+int cb_key_prefix_end(const uint8_t* prefix, uint64_t len, uint8_t* out, uint64_t* out_len, int* has_end) {
+  if ((len && (!prefix || !out)) || !out_len || !has_end) return fail(CB_EINVAL, "null argument");
+  *has_end = cb::key_prefix_end(prefix, len, out, out_len) ? 1 : 0;
+  return CB_OK;
+}
+
+int cb_tables_scan_prefix(const cb_table* const* tables, uint32_t nt, const uint8_t* prefix, uint64_t prefix_len,
+                          uint64_t limit, void* stream, void** out) {
+  if (!out) return fail(CB_EINVAL, "null argument");
+  *out = nullptr;
+  if (prefix_len && !prefix) return fail(CB_EINVAL, "null prefix with a length");
+  std::vector<uint8_t> end(prefix_len ? prefix_len : 1);
+  uint64_t end_len = 0;
+  const bool has_end = cb::key_prefix_end(prefix, prefix_len, end.data(), &end_len);
+  return cb_tables_scan(tables, nt, prefix, prefix_len, end.data(), end_len, has_end ? 1 : 0, limit, stream, out);
+}
+
+int cb_scan_info(const void* scan, uint64_t* count, uint64_t* key_bytes, uint64_t* val_bytes, int* truncated) {
+  const cb_scan* r = (const cb_scan*)scan;
+  if (!r) return fail(CB_EINVAL, "null scan");
+  if (count) *count = r->count;
+  if (key_bytes) *key_bytes = r->key_bytes;
+  if (val_bytes) *val_bytes = r->val_bytes;
+  if (truncated) *truncated = r->truncated ? 1 : 0;
+  return CB_OK;
+}
+
+namespace {
+// Offsets and bytes of a result into host or device memory (either may be NULL).
+int scan_copy(const cb_scan* r, uint64_t* off_out, const uint64_t* off, uint8_t* out, const uint8_t* bytes,
+              uint64_t nbytes) {
+  if (!r) return fail(CB_EINVAL, "null scan");
+  if (!r->count) {  // an empty result holds no device memory
+    const uint64_t zero = 0;
+    return off_out ? put_bytes((uint8_t*)off_out, &zero, 8) : CB_OK;
+  }
+  DeviceGuard dg(r->device);
+  if (off_out) HIP_TRY(hipMemcpy(off_out, off, (r->count + 1) * 8, hipMemcpyDefault));
+  if (out && nbytes) HIP_TRY(hipMemcpy(out, bytes, nbytes, hipMemcpyDefault));
+  return CB_OK;
+}
+}  // namespace
+
+int cb_scan_keys(const void* scan, uint64_t* key_off, uint8_t* keys) {
+  const cb_scan* r = (const cb_scan*)scan;
+  return scan_copy(r, key_off, r ? r->key_off : nullptr, keys, r ? r->keys : nullptr, r ? r->key_bytes : 0);
+}
+
+int cb_scan_values(const void* scan, uint64_t* val_off, uint8_t* vals) {
+  const cb_scan* r = (const cb_scan*)scan;
+  return scan_copy(r, val_off, r ? r->val_off : nullptr, vals, r ? r->vals : nullptr, r ? r->val_bytes : 0);
+}
+
+int cb_scan_which(const void* scan, int32_t* which) {
+  const cb_scan* r = (const cb_scan*)scan;
+  if (!r) return fail(CB_EINVAL, "null scan");
+  if (!r->count || !which) return CB_OK;
+  DeviceGuard dg(r->device);
+  HIP_TRY(hipMemcpy(which, r->which, r->count * 4, hipMemcpyDefault));
+  return CB_OK;
+}
+
+int cb_scan_destroy(void* scan) {
+  cb_scan* r = (cb_scan*)scan;
+  if (!r) return CB_OK;
+  pool_release(r->device, r->block, r->block_cap);
+  delete r;
   return CB_OK;
 }
 

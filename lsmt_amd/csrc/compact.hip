@@ -35,23 +35,6 @@ namespace {
 
 constexpr uint32_t kNT = kCompactTile;
 
-// The last i in [0, n) with at(i) <= x (at is non-decreasing, at(0) <= x).
-template <class At>
-__device__ __forceinline__ uint32_t last_le(uint32_t n, uint64_t x, At at) {
-  uint32_t lo = 0, hi = n;  // at(lo) <= x < at(hi) (at(n) = past every x)
-  while (hi - lo > 1) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (at(mid) <= x) lo = mid;
-    else hi = mid;
-  }
-  return lo;
-}
-
-// The source of global line g: the last one whose base is <= g.
-__device__ __forceinline__ uint32_t src_of(const CompactSrc* __restrict__ src, uint32_t nsrc, uint64_t g) {
-  return last_le(nsrc, g, [&](uint32_t i) { return src[i].base; });
-}
-
 __global__ __launch_bounds__(kNT) void k_compact_klen(const CompactSrc* __restrict__ src, uint32_t nsrc, uint64_t n,
                                                       uint64_t* __restrict__ klen) {
   const uint64_t g = (uint64_t)blockIdx.x * kNT + threadIdx.x;

@@ -29,6 +29,24 @@ struct CompactSrc {
   uint64_t base;
 };
 
+// The last i in [0, n) with at(i) <= x (at is non-decreasing, at(0) <= x).
+template <class At>
+__device__ __forceinline__ uint32_t last_le(uint32_t n, uint64_t x, At at) {
+  uint32_t lo = 0, hi = n;  // at(lo) <= x < at(hi) (at(n) = past every x)
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (at(mid) <= x) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// The source of global line g: the last one whose base is <= g (no two
+// sources share a base: every source has lines).
+__device__ __forceinline__ uint32_t src_of(const CompactSrc* __restrict__ src, uint32_t nsrc, uint64_t g) {
+  return last_le(nsrc, g, [&](uint32_t i) { return src[i].base; });
+}
+
 // What the later passes need of input line g once the sort has moved its
 // record: where `key \t text` starts, its length (the line without '\n'), the
 // key's length and the value's decoded length.

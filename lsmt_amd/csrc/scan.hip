@@ -1,0 +1,259 @@
+// scan.hip — the kernels of cb_tables_scan (scan.hpp): cut every table to
+// the range, hand the cuts to compaction's merge as its sources, and emit the
+// survivors' keys, sources and value spans.
+//
+//   k_scan_bounds — sixteen lanes per (table, bound): the lower bound of the
+//       bound's zero-padded 8-byte prefix down the table's fence levels, each
+//       level one run of at most 16 entries read by the sixteen lanes at once
+//       (one 128-B line, one round trip per level where a bisection takes
+//       four), then the lines that share the prefix by record compares, again
+//       sixteen probes a round. A lower-bound search: it never asks whether
+//       the bound is a key of the table. The searches are few (two per table)
+//       and each is a short chain of dependent loads, so the kernel is as
+//       long as one table's descent.
+//   k_scan_sources — one block: the scan of the cuts' lengths, the non-empty
+//       cuts packed as CompactSrc entries (rec + first, llen + first).
+//   k_scan_emit — one block per tile of sorted records, as k_compact_format:
+//       the survivors' ranks and key offsets from the scanned tile sums and a
+//       block scan, the tile's key bytes assembled into aligned dwords, and
+//       per survivor its key offset, source and value span. A tile's
+//       survivors lie in at most two of the decode's tiles, so the block adds
+//       two partial sums of their decoded lengths.
+#include <hip/hip_runtime.h>
+
+#include "blockscan.hpp"
+#include "launch.hpp"
+#include "profile.hpp"
+#include "scan.hpp"
+#include "tablesearch.hpp"
+
+namespace cb {
+namespace {
+
+constexpr uint32_t kNT = 256;
+constexpr uint32_t kGroup = 16;  // lanes per search
+static_assert(kGroup == kFanout, "a group reads one run of a fence level at once");
+static_assert(kCompactTile == kNT && kDecodeTile == kNT, "k_scan_emit's tiles");
+
+// How many lanes of this lane's group hold pred (every lane of the group
+// calls it together; other groups of the wave may be elsewhere).
+__device__ __forceinline__ uint32_t group_count(bool pred) {
+  const uint64_t b = __ballot(pred);
+  return (uint32_t)__builtin_popcount((uint32_t)(b >> (threadIdx.x & 48u)) & 0xFFFFu);
+}
+
+// The first i in [lo, hi) for which below(i) is false, or hi (below is true
+// on a prefix of the range): sixteen evenly spaced probes a round, so a run of
+// at most 16 takes one round.
+template <class Below>
+__device__ __forceinline__ uint64_t group_lower_bound(uint64_t lo, uint64_t hi, uint32_t sub, Below below) {
+  while (lo < hi) {  // (the same for every lane of the group)
+    const uint64_t step = (hi - lo + kGroup - 1) / kGroup;
+    const uint64_t p = lo + sub * step;
+    const uint32_t c = group_count(p < hi && below(p));
+    if (!c) break;
+    // probes 0..c-1 are below, probe c is not (or lies past hi)
+    const uint64_t nhi = lo + c * step < hi ? lo + c * step : hi;
+    lo += (c - 1) * step + 1;
+    hi = nhi;
+  }
+  return lo;
+}
+
+// The first entry of level 0 (pfx) that is >= x (strict) or > x, down the levels.
+__device__ __forceinline__ uint64_t group_descend(const TableView& v, uint64_t x, bool strict, uint32_t sub) {
+  uint32_t j = v.nlev();
+  uint64_t lo = 0, hi = level_count(v.nlines(), j);
+  for (;; --j) {
+    const uint64_t* a = level_array(v, j);
+    const uint64_t i = group_lower_bound(lo, hi, sub, [&](uint64_t p) {
+      const uint64_t e = g64(a, p);
+      return strict ? e < x : e <= x;
+    });
+    if (!j) return i;
+    level_down(v, j, i, lo, hi);
+  }
+}
+
+// The first line of v whose key is >= q.
+__device__ __forceinline__ uint64_t group_bound(const TableView& v, const Query& q, uint32_t sub) {
+  const uint64_t nl = v.nlines();
+  const uint64_t i0 = group_descend(v, q.w0, true, sub);
+  // the lines from i0 on that share q's prefix: the next 16 prefixes, and a
+  // second descent only when they all do
+  const uint32_t c = group_count(i0 + sub < nl && g64(v.pfx, i0 + sub) == q.w0);
+  if (!c) return i0;
+  uint64_t e = i0 + c;
+  if (c == kGroup && e < nl) e = group_descend(v, q.w0, false, sub);
+  return group_lower_bound(i0, e, sub, [&](uint64_t l) { return rec_cmp(v, grec(v.rec, l), q) < 0; });
+}
+
+__global__ __launch_bounds__(kNT) void k_scan_bounds(const ScanTable* __restrict__ tab, uint32_t nt, ScanRange range,
+                                                     ScanCut* __restrict__ cut) {
+  const uint32_t sub = threadIdx.x & (kGroup - 1);
+  const uint64_t nq = 2ull * nt;  // search 2 t: table t's lo, 2 t + 1: its hi
+  uint64_t g = ((uint64_t)blockIdx.x * kNT + threadIdx.x) / kGroup;
+  const bool live = g < nq;
+  if (!live) g = nq - 1;  // (the last groups repeat the last search: every lane stays in step)
+  const uint32_t t = (uint32_t)(g >> 1);
+  const bool upper = g & 1;
+  const ScanTable st = tab[t];
+  const TableView v =
+      make_view(st.data, st.rec, st.pfx, st.fence, st.nlines, fence_levels(st.nlines), true, nullptr, nullptr);
+  Query q;
+  q.p = range.bytes + (upper ? range.hi_at : 0);
+  q.len = upper ? range.hi_len : range.lo_len;
+  q.w0 = be_chunk(q.p, q.len < 8 ? q.len : 8);
+  q.w1 = q.len > 8 ? be_chunk(q.p + 8, q.len - 8 < 8 ? q.len - 8 : 8) : 0;
+  unsigned long long b = st.nlines;
+  if (!upper || range.has_hi) b = group_bound(v, q, sub);
+  const unsigned long long hi_b = __shfl_down(b, kGroup, 64);  // the table's hi search: the next group
+  if (live && !upper && sub == 0) {
+    ScanCut c;
+    c.first = b;
+    c.last = hi_b > b ? hi_b : b;  // lo >= hi: an empty cut
+    const uint64_t end = c.last < st.nlines ? grec(st.rec, c.last).start : st.len;
+    c.bytes = c.last > c.first ? end - grec(st.rec, c.first).start : 0;
+    cut[t] = c;
+  }
+}
+
+__global__ __launch_bounds__(kNT) void k_scan_sources(const ScanTable* __restrict__ tab,
+                                                      const ScanCut* __restrict__ cut, uint32_t nt,
+                                                      CompactSrc* __restrict__ src, uint32_t* __restrict__ src_tab,
+                                                      uint64_t* __restrict__ totals) {
+  uint64_t base = 0, bytes = 0, ns = 0;
+  for (uint32_t t0 = 0; t0 < nt; t0 += kNT) {
+    const uint32_t t = t0 + threadIdx.x;
+    ScanCut c{0, 0, 0};
+    if (t < nt) c = cut[t];
+    const uint64_t len = c.last - c.first;
+    uint64_t tl, tn, tb, unused;
+    const uint64_t off = block_scan<(int)kNT>(len, &tl);
+    const uint64_t si = block_scan_sum2<(int)kNT>(len ? 1 : 0, c.bytes, 0, &tn, &tb, &unused);
+    if (len) {
+      const ScanTable st = tab[t];
+      src[ns + si] = CompactSrc{st.data, st.rec + c.first, st.llen + c.first, base + off};
+      src_tab[ns + si] = st.index;
+    }
+    base += tl;
+    bytes += tb;
+    ns += tn;
+  }
+  if (threadIdx.x == 0) {
+    totals[0] = base;
+    totals[1] = bytes;
+    totals[2] = ns;
+  }
+}
+
+__global__ __launch_bounds__(kNT) void k_scan_emit(const SortKey* __restrict__ order,
+                                                   const CompactSide* __restrict__ side,
+                                                   const uint64_t* __restrict__ slen,
+                                                   const uint64_t* __restrict__ tcnt,
+                                                   const uint64_t* __restrict__ tkeys,
+                                                   const uint64_t* __restrict__ totals,
+                                                   const CompactSrc* __restrict__ src,
+                                                   const uint32_t* __restrict__ src_tab, uint32_t nsrc, uint64_t n,
+                                                   uint64_t count, uint8_t* __restrict__ keys,
+                                                   uint64_t* __restrict__ key_off, int32_t* __restrict__ which,
+                                                   uint64_t* __restrict__ vsrc, uint64_t* __restrict__ dlen,
+                                                   uint64_t* __restrict__ vsum) {
+  __shared__ uint64_t s_off[kNT + 1];    // survivor i's first key byte in the tile
+  __shared__ const uint8_t* s_src[kNT];  // its key
+  const uint64_t p = (uint64_t)blockIdx.x * kNT + threadIdx.x;
+  const bool live = p < n && slen[p] != 0;
+  CompactSide sd{};
+  uint32_t g = 0;
+  if (live) {
+    g = order[p].idx;
+    sd = side[g];
+  }
+  const uint64_t r0 = tcnt[blockIdx.x];  // the tile's first rank
+  uint64_t tc, tk;
+  const uint64_t ci = block_scan<(int)kNT>(live ? 1 : 0, &tc);
+  const uint64_t kof = block_scan<(int)kNT>(live ? sd.klen : 0, &tk);
+  const uint64_t r = r0 + ci;
+  const bool out = live && r < count;
+  // the decode's tile sums: ranks r0 .. r0 + tc lie in tile r0 / 256 and the next
+  const uint64_t split = (r0 / kDecodeTile + 1) * kDecodeTile;
+  uint64_t unused, va, vb;
+  (void)block_scan_sum2<(int)kNT>(0, out && r < split ? sd.vdl : 0, out && r >= split ? sd.vdl : 0, &unused, &va,
+                                  &vb);
+  if (threadIdx.x == 0) {
+    if (va) atomicAdd((unsigned long long*)(vsum + r0 / kDecodeTile), (unsigned long long)va);
+    if (vb) atomicAdd((unsigned long long*)(vsum + r0 / kDecodeTile + 1), (unsigned long long)vb);
+    if (blockIdx.x == 0 && count == totals[0]) key_off[count] = totals[2];  // no limit cut: the end of all keys
+  }
+  if (live) {
+    s_off[ci] = kof;
+    s_src[ci] = sd.src;
+    // (rank == count: the first survivor past the limit, whose key offset is the end of the kept keys)
+    if (r <= count) key_off[r] = tkeys[blockIdx.x] + kof;
+  }
+  if (out) {
+    which[r] = (int32_t)src_tab[src_of(src, nsrc, g)];
+    vsrc[r] = (uint64_t)(uintptr_t)(sd.src + sd.klen + 1);
+    dlen[r] = sd.vdl;
+  }
+  if (threadIdx.x == 0) s_off[tc] = tk;
+  __syncthreads();
+  const uint32_t nsv = r0 >= count ? 0u : (uint32_t)(count - r0 < tc ? count - r0 : tc);  // survivors under the limit
+  if (!nsv) return;  // (uniform)
+  const uint64_t tl = s_off[nsv];
+  // byte j of the tile's keys: survivor i = the last with s_off[i] <= j (an
+  // empty key owns no byte: the last of equal offsets is the one that does)
+  auto key_of = [&](uint64_t j) { return last_le(nsv, j, [&](uint32_t i) { return s_off[i]; }); };
+  auto byte_at = [&](uint32_t i, uint64_t j) -> uint32_t { return s_src[i][j - s_off[i]]; };
+  // keys[base .. base + tl): bytes up to the first 4-aligned address, then
+  // aligned dwords, then the tail
+  uint8_t* o = keys + tkeys[blockIdx.x];
+  const uint64_t mis = (4 - ((uintptr_t)o & 3)) & 3;
+  const uint64_t head = mis < tl ? mis : tl;
+  if (threadIdx.x < head) o[threadIdx.x] = (uint8_t)byte_at(key_of(threadIdx.x), threadIdx.x);
+  const uint64_t body = (tl - head) / 4;
+  uint32_t* ow = reinterpret_cast<uint32_t*>(o + head);
+  for (uint64_t w = threadIdx.x; w < body; w += kNT) {
+    const uint64_t j0 = head + 4 * w;
+    uint32_t i = key_of(j0), x = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < 4; ++k) {
+      while (j0 + k >= s_off[i + 1]) ++i;  // (j0 + k < tl = s_off[nsv]: stops at a survivor)
+      x |= byte_at(i, j0 + k) << (8 * k);
+    }
+    ow[w] = x;
+  }
+  const uint64_t tail0 = head + 4 * body;
+  if (tail0 + threadIdx.x < tl) o[tail0 + threadIdx.x] = (uint8_t)byte_at(key_of(tail0 + threadIdx.x), tail0 + threadIdx.x);
+}
+
+}  // namespace
+
+hipError_t launch_scan_bounds(const ScanTable* tab, uint32_t nt, const ScanRange& range, ScanCut* cut,
+                              hipStream_t s) {
+  if (!nt) return hipSuccess;
+  ProfScope ps("k_scan_bounds", s);
+  hipLaunchKernelGGL(k_scan_bounds, dim3(blocks_for(2ull * nt * kGroup, kNT)), dim3(kNT), 0, s, tab, nt, range, cut);
+  return hipGetLastError();
+}
+
+hipError_t launch_scan_sources(const ScanTable* tab, const ScanCut* cut, uint32_t nt, CompactSrc* src,
+                               uint32_t* src_tab, uint64_t* totals, hipStream_t s) {
+  ProfScope ps("k_scan_sources", s);
+  hipLaunchKernelGGL(k_scan_sources, dim3(1), dim3(kNT), 0, s, tab, cut, nt, src, src_tab, totals);
+  return hipGetLastError();
+}
+
+hipError_t launch_scan_emit(const SortKey* order, const CompactSide* side, const uint64_t* slen,
+                            const uint64_t* tcnt, const uint64_t* tkeys, const uint64_t* totals,
+                            const CompactSrc* src, const uint32_t* src_tab, uint32_t nsrc, uint64_t n, uint64_t count,
+                            uint8_t* keys, uint64_t* key_off, int32_t* which, uint64_t* vsrc, uint64_t* dlen,
+                            uint64_t* vsum, hipStream_t s) {
+  if (!n || !count) return hipSuccess;
+  ProfScope ps("k_scan_emit", s);
+  hipLaunchKernelGGL(k_scan_emit, dim3(blocks_for(n, kNT)), dim3(kNT), 0, s, order, side, slen, tcnt, tkeys, totals,
+                     src, src_tab, nsrc, n, count, keys, key_off, which, vsrc, dlen, vsum);
+  return hipGetLastError();
+}
+
+}  // namespace cb
