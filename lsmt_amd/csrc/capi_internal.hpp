@@ -2,9 +2,11 @@
 // (capi_runtime.cpp: errors, the block pool, workspaces, staging;
 // capi_filter.cpp: filters, insert / probe, the codec's device halves;
 // capi_set.cpp: filter sets, zones, tiers, the exchange entries;
-// capi_sstable.cpp: SSTable files, the read path and SsTable::create): the
-// handle structs, error reporting, device buffers, the block pool, per-stream
-// workspaces and the host frame around a keyed launch.
+// capi_table.cpp, capi_flush.cpp, capi_get.cpp, capi_merge.cpp: SSTable files,
+// SsTable::create, the read path, compaction and scans; those four share
+// capi_table.hpp besides): the handle structs, error reporting, device
+// buffers, the block pool, per-stream workspaces and the host frame around a
+// keyed launch.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -151,11 +153,11 @@ inline cb::WideZone wide_zone_view(const cb_filterset* set) {
 }
 
 // What a table made by cb_sstable_create still owes the host until its
-// enqueued work has run (capi_sstable.cpp finalize_table): the event after
+// enqueued work has run (capi_flush.cpp finalize_table): the event after
 // the result copy, the pinned result block, and what a fallback sort needs
 // (the batch: the caller's device buffers, or the table's own staged copy).
 // Owns the staged block and the result slot of an enqueued SsTable::create;
-// the destructor returns both (capi_sstable.cpp), so an error return from the
+// the destructor returns both (capi_flush.cpp), so an error return from the
 // enqueue leaks neither. Destroy it only once its work can no longer run
 // (finalised, or the stream synchronised).
 struct TablePending {
@@ -204,7 +206,7 @@ struct cb_table {
   int ferr = 0;
   std::string ferr_msg;
   // The read path's key buckets (sstable.hpp), built by the table's first
-  // get_many on that call's stream (capi_sstable.cpp table_buckets); every
+  // get_many on that call's stream (capi_get.cpp table_buckets); every
   // later read enqueues a wait on bkt_ev until it has been seen complete.
   uint64_t* bkt = nullptr;
   size_t bkt_cap = 0;
@@ -284,9 +286,9 @@ struct Workspace {
   DevBuf keys, offsets, hits, seg, ent, masks, bools, lkey, zone;
   DevBuf t_views, t_rows, t_which, t_line, t_dlen, t_voff, t_scan, t_vals;
   // what t_views / t_rows / t_groups hold, as bytes (a call with the same
-  // tables, rows and groups uploads nothing: capi_sstable.cpp upload_if_changed)
+  // tables, rows and groups uploads nothing: capi_get.cpp upload_if_changed)
   std::vector<uint8_t> t_views_host, t_rows_host, t_groups_host;
-  DevBuf t_groups;                          // a wide set's table groups (cb::WideGroup)
+  DevBuf t_groups;                          // a wide set's table groups (tablehost.hpp WideGroup)
   DevBuf t_maps;                            // the tables' DirMaps, contiguous (the wide walk stages them)
   std::vector<uint64_t> t_maps_sig;         // what t_maps was gathered from (table uids and map pointers)
   DevBuf w_scr;                             // the wide walk's screen (sstable.hpp WideScreen)
@@ -411,7 +413,7 @@ int insert_locked(Workspace& ws, cb_filter* f, const uint8_t* keys, const uint64
                   uint32_t key_len, uint64_t n, hipStream_t s);
 // A table from cb_sstable_create: wait for its enqueued work and take its
 // results (once; thread-safe). Returns the table's deferred error, if any.
-// Every entry point that reads a table calls it first (capi_sstable.cpp).
+// Every entry point that reads a table calls it first (capi_flush.cpp).
 int finalize_table(cb_table* t);
 // Host bytes into an output buffer that may be host or device memory.
 int put_bytes(uint8_t* dst, const void* src, size_t n);

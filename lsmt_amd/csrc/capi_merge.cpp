@@ -1,0 +1,514 @@
+// capi_merge.cpp — merging SSTables on the device: the newest-wins merge
+// (compact.hpp) and its two users, compaction into one new table
+// (cb_tables_compact) and range and prefix scans into a result
+// (cb_tables_scan, scan.hpp), with the result's accessors (cb_scan_*).
+//
+// Reference: src/sstable.rs:51-98 (the file a compaction writes),
+// src/lib.rs:125-146 (Database::get, whose answers both reproduce).
+#include "capi_table.hpp"
+#include "compact.hpp"
+#include "keyrange.hpp"
+#include "scan.hpp"
+
+using namespace cbx;
+
+namespace {
+
+// ---- the table list both entries take ----
+
+// A non-empty list without a null table, all on one device (*dev).
+int check_table_list(const cb_table* const* tables, uint32_t nt, int* dev) {
+  if (!nt || !tables) return fail(CB_EINVAL, "no tables");
+  for (uint32_t i = 0; i < nt; ++i)
+    if (!tables[i]) return fail(CB_EINVAL, "null table");
+  *dev = tables[0]->device;
+  for (uint32_t i = 0; i < nt; ++i)
+    if (tables[i]->device != *dev) return fail(CB_EINVAL, "tables live on different devices");
+  return CB_OK;
+}
+
+// each(table, its place in the list) for the non-empty tables, newest first:
+// every table is finalised on the way, and one that is not well-formed refused.
+template <class Each>
+int for_live_tables(const cb_table* const* tables, uint32_t nt, Each each) {
+  for (uint32_t i = 0; i < nt; ++i) {
+    cb_table* ti = const_cast<cb_table*>(tables[i]);
+    if (int rc = finalize_table(ti)) return rc;
+    if (!ti->nlines) continue;
+    if (!ti->fast) return fail(CB_EINVAL, "an input table is not well-formed");
+    each(ti, i);
+  }
+  return CB_OK;
+}
+
+// ---- the merge ----
+
+// The newest-wins merge that cb_tables_compact and cb_tables_scan run over
+// their sources (compact.hpp): the lines' keys gathered into one batch, the
+// stable key sort, the select of each key's newest decodable line and the
+// scanned tile sums of the survivors. Its scratch is one pool block.
+struct Merge {
+  uint64_t n = 0, kbound = 0, tiles = 0;  // lines, a bound on their keys' bytes, select tiles
+  SortPlan plan{};
+  cb::CompactSrc* dsrc = nullptr;  // room for the caller's sources (nsrc_cap of them)
+  uint64_t *klen = nullptr, *ko = nullptr, *scan = nullptr;
+  uint8_t* kb = nullptr;
+  cb::CompactSide* side = nullptr;
+  cb::SortKey* order = nullptr;
+  uint8_t* sort = nullptr;
+  uint64_t *slen = nullptr, *tcnt = nullptr, *tbytes = nullptr, *tkeys = nullptr, *tot = nullptr;
+  cb::CreateResult* dr = nullptr;
+};
+int merge_alloc(uint32_t nsrc_cap, uint64_t n, uint64_t kbound, TempBlock& tmp, Merge* m) {
+  m->n = n;
+  m->kbound = kbound;
+  m->tiles = cb::compact_tiles(n);
+  m->plan = plan_key_sort(n);  // the order: sorted as cb_sstable_create sorts a batch
+  cb::Carver c;
+  const size_t o_src = c.take(nsrc_cap * sizeof(cb::CompactSrc)), o_klen = c.take(n * 8), o_ko = c.take((n + 1) * 8),
+               o_scan = c.take(cb::scan_tmp_words(n) * 8), o_kb = c.take(kbound + 16),
+               o_side = c.take(n * sizeof(cb::CompactSide)), o_order = c.take(n * sizeof(cb::SortKey)),
+               o_sort = c.take(m->plan.tmp_bytes), o_slen = c.take(n * 8), o_tcnt = c.take(m->tiles * 8),
+               o_tbytes = c.take(m->tiles * 8), o_tkeys = c.take(m->tiles * 8), o_tot = c.take(3 * 8),
+               o_res = c.take(sizeof(cb::CreateResult));
+  if (int rc = tmp.alloc(c, "device allocation failed for a merge's scratch")) return rc;
+  m->dsrc = (cb::CompactSrc*)tmp.at(o_src);
+  m->klen = (uint64_t*)tmp.at(o_klen);
+  m->ko = (uint64_t*)tmp.at(o_ko);
+  m->scan = (uint64_t*)tmp.at(o_scan);
+  m->kb = tmp.at(o_kb);
+  m->side = (cb::CompactSide*)tmp.at(o_side);
+  m->order = (cb::SortKey*)tmp.at(o_order);
+  m->sort = tmp.at(o_sort);
+  m->slen = (uint64_t*)tmp.at(o_slen);
+  m->tcnt = (uint64_t*)tmp.at(o_tcnt);
+  m->tbytes = (uint64_t*)tmp.at(o_tbytes);
+  m->tkeys = (uint64_t*)tmp.at(o_tkeys);
+  m->tot = (uint64_t*)tmp.at(o_tot);
+  m->dr = (cb::CreateResult*)tmp.at(o_res);
+  return CB_OK;
+}
+// The merge of sources dsrc[0..nsrc) (device, m.n lines in all) on s, up to
+// the survivors' totals h = {lines, file bytes, key bytes}: read back (they
+// size the caller's output), the stream waited for, and checked against the
+// inputs' bounds before anything is sized from them.
+int enqueue_merge(const Merge& m, const cb::CompactSrc* dsrc, uint32_t nsrc, hipStream_t s, uint64_t (&h)[3]) {
+  const uint64_t n = m.n;
+  HIP_TRY(cb::launch_compact_klen(dsrc, nsrc, n, m.klen, s));
+  HIP_TRY(cb::launch_scan_u64(m.klen, m.ko, n, m.scan, s));
+  // the bin sort's inputs: an unsorted batch (flags[0]) and its prefix byte masks
+  HIP_TRY(hipMemsetAsync(m.dr, 0, cb::kCreateHead, s));
+  HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)&m.dr->flags[0], 1, 1, s));
+  HIP_TRY(cb::launch_compact_gather(dsrc, nsrc, n, m.ko, m.kb, m.side, &m.dr->dmask[0][0], s));
+  // the stable sort by key, input index last: a key's lines leave it
+  // adjacent, newest first
+  if (int rc = enqueue_key_sort(m.plan, m.kb, m.ko, n, m.order, m.sort, m.dr, s, nullptr, nullptr, nullptr)) return rc;
+  HIP_TRY(cb::launch_compact_select(m.order, m.side, m.kb, m.ko, n, m.slen, m.tcnt, m.tbytes, m.tkeys, s));
+  HIP_TRY(cb::launch_tile_scan(m.tcnt, m.tiles, m.tot + 0, s));
+  HIP_TRY(cb::launch_tile_scan(m.tbytes, m.tiles, m.tot + 1, s));
+  HIP_TRY(cb::launch_tile_scan(m.tkeys, m.tiles, m.tot + 2, s));
+  h[0] = h[1] = h[2] = 0;
+  HIP_TRY(hipMemcpyAsync(h, m.tot, sizeof h, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (h[0] > n || h[2] > m.kbound || h[1] > m.kbound + n) return fail(CB_EHIP, "merge: inconsistent totals");
+  return CB_OK;
+}
+
+// ---- cb_tables_compact's steps, in the order it takes them ----
+
+// The kept keys as one batch (device, in a block of the call's).
+struct KeptKeys {
+  uint8_t* kb = nullptr;
+  uint64_t* ko = nullptr;
+};
+
+// 1: the sources: the non-empty tables, newest first, with their line bases;
+// n their lines, kbound a bound on their keys' bytes.
+int compact_sources(const cb_table* const* tables, uint32_t nt, std::vector<cb::CompactSrc>& srcs, uint64_t* n,
+                    uint64_t* kbound) {
+  if (int rc = for_live_tables(tables, nt, [&](cb_table* ti, uint32_t) {
+        srcs.push_back(cb::CompactSrc{ti->data, ti->rec, ti->llen, *n});
+        *n += ti->nlines;
+        *kbound += ti->len;  // the keys' bytes are among the file's
+      }))
+    return rc;
+  if (*n > 0xFFFFFFFFull) return fail(CB_EINVAL, "too many lines for one compaction");
+  return CB_OK;
+}
+
+// 2: the merge over the sources, staged into its scratch (one wait: the
+// source is pageable), up to the survivors' totals h (enqueue_merge's wait).
+int merge_sources(const std::vector<cb::CompactSrc>& srcs, uint64_t n, uint64_t kbound, TempBlock& tmp, Merge* mg,
+                  hipStream_t s, uint64_t (&h)[3]) {
+  const uint32_t nsrc = (uint32_t)srcs.size();
+  if (int rc = merge_alloc(nsrc, n, kbound, tmp, mg)) return rc;
+  HIP_TRY(hipMemcpyAsync(mg->dsrc, srcs.data(), nsrc * sizeof(cb::CompactSrc), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipStreamSynchronize(s));  // the source is pageable
+  return enqueue_merge(*mg, mg->dsrc, nsrc, s, h);
+}
+
+// 3: the survivors (h = {lines, file bytes, key bytes}) formatted into t: the
+// file and its line index in one pass (the file is not re-read), and the kept
+// keys beside them. No survivor: the file's buffer alone.
+int format_survivors(cb_table* t, const Merge& mg, const uint64_t (&h)[3], TempBlock& keys, KeptKeys* k,
+                     hipStream_t s) {
+  const uint64_t cnt = h[0], len = h[1], kbytes = h[2];
+  t->len = len;
+  if (int rc = alloc_file(t, len + 16)) return rc;
+  HIP_TRY(hipMemsetAsync(t->data + len, 0, 16, s));
+  if (!cnt) return CB_OK;
+  if (int rc = alloc_index(t, cnt)) return rc;
+  cb::Carver c;
+  const size_t o_kb = c.take(kbytes + 16), o_ko = c.take((cnt + 1) * 8);
+  if (int rc = keys.alloc(c, "device allocation failed for a compaction's keys")) return rc;
+  k->kb = keys.at(o_kb);
+  k->ko = (uint64_t*)keys.at(o_ko);
+  HIP_TRY(cb::launch_compact_format(mg.order, mg.side, mg.slen, mg.tcnt, mg.tbytes, mg.tkeys, mg.tot, mg.n, cnt,
+                                    t->data, t->rec, t->pfx, t->fence, t->llen, k->kb, k->ko, s));
+  return CB_OK;
+}
+
+// 5: the directory's map from the new prefixes (the merge's masks are
+// reused) and the zone map's bounds, the first and last kept key: their
+// offsets come back with the masks (one wait), their bytes after the
+// directory is enqueued (one more: the zone bounds are host results).
+int finish_compacted(cb_table* t, const Merge& mg, const KeptKeys& k, const uint64_t (&h)[3], hipStream_t s) {
+  const uint64_t cnt = h[0], kbytes = h[2];
+  uint64_t* dmask = &mg.dr->dmask[0][0];
+  if (int rc = enqueue_pfx_masks(t, dmask, s)) return rc;
+  uint64_t e[2] = {0, 0}, m[cb::kDirPos][4] = {};
+  HIP_TRY(hipMemcpyAsync(&e[0], k.ko + 1, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(&e[1], k.ko + cnt - 1, 8, hipMemcpyDeviceToHost, s));
+  if (t->dir) HIP_TRY(hipMemcpyAsync(m, dmask, sizeof m, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (e[0] > kbytes || e[1] > kbytes) return fail(CB_EHIP, "compaction: inconsistent key offsets");
+  if (int rc = enqueue_directory(t, m, s)) return rc;
+  t->zmin.resize(e[0]);
+  t->zmax.resize(kbytes - e[1]);
+  if (e[0]) HIP_TRY(hipMemcpyAsync(&t->zmin[0], k.kb, e[0], hipMemcpyDeviceToHost, s));
+  if (kbytes - e[1]) HIP_TRY(hipMemcpyAsync(&t->zmax[0], k.kb + e[1], kbytes - e[1], hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  // strictly increasing keys, a TAB on every line: by construction
+  t->fast = !table_exact();
+  t->has_zone = true;
+  return CB_OK;
+}
+
+// ---- the scan result ----
+
+int scan_alloc(cb_scan* r, uint64_t count, uint64_t kb, uint64_t vb) {
+  size_t o[5];
+  const size_t bytes = cb::scan_layout(count, kb, vb, o);
+  if (int rc = pool_alloc_or(r->device, bytes, &r->block, &r->block_cap,
+                             "device allocation failed for a scan's result"))
+    return rc;
+  uint8_t* b = (uint8_t*)r->block;
+  r->key_off = (uint64_t*)(b + o[0]);
+  r->val_off = (uint64_t*)(b + o[1]);
+  r->which = (int32_t*)(b + o[2]);
+  r->keys = b + o[3];
+  r->vals = b + o[4];
+  return CB_OK;
+}
+
+// ---- cb_tables_scan's steps, in the order it takes them ----
+
+// What step 2 leaves on the device for the merge and the emit (in the call's
+// `cuts` block), and the cuts' totals.
+struct ScanCuts {
+  const cb::CompactSrc* dsrc = nullptr;  // the cuts as the merge's sources
+  const uint32_t* dmap = nullptr;        // each source's place in the caller's list
+  uint64_t n = 0, kbound = 0;            // lines inside the range, a bound on their keys' bytes
+  uint32_t nsrc = 0;
+};
+
+// 1: the arguments: the list, then the bounds (without has_hi, hi is ignored).
+int check_scan_args(const cb_table* const* tables, uint32_t nt, const uint8_t* lo, uint64_t lo_len, const uint8_t* hi,
+                    uint64_t* hi_len, int has_hi, int* dev) {
+  if (int rc = check_table_list(tables, nt, dev)) return rc;
+  if (lo_len && !lo) return fail(CB_EINVAL, "null lower bound with a length");
+  if (!has_hi) *hi_len = 0;
+  if (*hi_len && !hi) return fail(CB_EINVAL, "null upper bound with a length");
+  return CB_OK;
+}
+
+// 2: every table's cut, and the cuts as the merge's sources. Two waits: after
+// staging the tables and the bounds (pageable memory), and for the cuts'
+// totals, checked against the tables' (all_lines, all_bytes) before anything
+// is sized from them.
+int cut_tables(const std::vector<cb::ScanTable>& tabs, uint64_t all_lines, uint64_t all_bytes, const uint8_t* lo,
+               uint64_t lo_len, const uint8_t* hi, uint64_t hi_len, int has_hi, TempBlock& cuts, hipStream_t s,
+               ScanCuts* out) {
+  const uint32_t ntab = (uint32_t)tabs.size();
+  cb::Carver c;
+  const size_t o_tab = c.take(ntab * sizeof(cb::ScanTable)), o_bnd = c.take(lo_len + hi_len + 16);
+  const size_t up_bytes = c.total();  // (the two parts staged from the host)
+  const size_t o_cut = c.take(ntab * sizeof(cb::ScanCut)), o_src = c.take(ntab * sizeof(cb::CompactSrc)),
+               o_map = c.take(ntab * 4), o_ctot = c.take(3 * 8);
+  if (int rc = cuts.alloc(c, "device allocation failed for a scan's cuts")) return rc;
+  std::vector<uint8_t> up(up_bytes, 0);
+  std::memcpy(&up[o_tab], tabs.data(), ntab * sizeof(cb::ScanTable));
+  if (lo_len) std::memcpy(&up[o_bnd], lo, lo_len);
+  if (hi_len) std::memcpy(&up[o_bnd + lo_len], hi, hi_len);
+  HIP_TRY(hipMemcpyAsync(cuts.p, up.data(), up_bytes, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipStreamSynchronize(s));  // the source is pageable
+  const cb::ScanTable* dtab = (const cb::ScanTable*)cuts.at(o_tab);
+  cb::ScanCut* dcut = (cb::ScanCut*)cuts.at(o_cut);
+  cb::CompactSrc* dsrc = (cb::CompactSrc*)cuts.at(o_src);
+  uint32_t* dmap = (uint32_t*)cuts.at(o_map);
+  uint64_t* dctot = (uint64_t*)cuts.at(o_ctot);
+  const cb::ScanRange range{cuts.at(o_bnd), lo_len, lo_len, hi_len, has_hi ? 1u : 0u, 0};
+  HIP_TRY(cb::launch_scan_bounds(dtab, ntab, range, dcut, s));
+  HIP_TRY(cb::launch_scan_sources(dtab, dcut, ntab, dsrc, dmap, dctot, s));
+  uint64_t t[3] = {0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(t, dctot, sizeof t, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  const uint64_t n = t[0], kbound = t[1], nsrc = t[2];
+  if (n > all_lines || kbound > all_bytes || nsrc > ntab || nsrc > n || (n && !nsrc))
+    return fail(CB_EHIP, "scan: inconsistent cut totals");
+  if (n > 0xFFFFFFFFull) return fail(CB_EINVAL, "too many lines inside the range for one scan");
+  *out = ScanCuts{dsrc, dmap, n, kbound, (uint32_t)nsrc};
+  return CB_OK;
+}
+
+// 4: the result's block for `count` entries (room for kbytes key bytes and
+// vcap value bytes) and, in it, the kept keys, their offsets and sources;
+// the kept values' spans go into v, scratch in vtmp, for the decode.
+int emit_scan_result(cb_scan* r, const Merge& mg, const ScanCuts& c, uint64_t count, uint64_t kbytes, uint64_t vcap,
+                     TempBlock& vtmp, hipStream_t s, ValueSpans* v) {
+  if (int rc = scan_alloc(r, count, kbytes, vcap)) return rc;
+  const uint64_t vtiles = cb::get_tiles(count);
+  cb::Carver vc;
+  const size_t o_vsrc = vc.take(count * 8), o_dlen = vc.take(count * 8), o_vsum = vc.take(vtiles * 8);
+  if (int rc = vtmp.alloc(vc, "device allocation failed for a scan's value spans")) return rc;
+  uint64_t *vsrc = (uint64_t*)vtmp.at(o_vsrc), *dlen = (uint64_t*)vtmp.at(o_dlen), *vsum = (uint64_t*)vtmp.at(o_vsum);
+  HIP_TRY(hipMemsetAsync(vsum, 0, vtiles * 8, s));
+  HIP_TRY(cb::launch_scan_emit(mg.order, mg.side, mg.slen, mg.tcnt, mg.tkeys, mg.tot, c.dsrc, c.dmap, c.nsrc, mg.n,
+                               count, r->keys, r->key_off, r->which, vsrc, dlen, vsum, s));
+  *v = ValueSpans{vsrc, dlen, vsum, r->val_off};
+  return CB_OK;
+}
+
+// 6: the kept keys' and values' byte totals (one wait: the result is complete
+// when the call returns), checked against what the block was sized for.
+int take_scan_totals(cb_scan* r, uint64_t count, uint64_t cnt, uint64_t kbytes, uint64_t vcap, hipStream_t s) {
+  uint64_t e[2] = {0, 0};
+  HIP_TRY(hipMemcpyAsync(&e[0], r->key_off + count, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(&e[1], r->val_off + count, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (e[0] > kbytes || e[1] > vcap) return fail(CB_EHIP, "scan: inconsistent result totals");
+  r->count = count;
+  r->key_bytes = e[0];
+  r->val_bytes = e[1];
+  r->truncated = count < cnt;
+  return CB_OK;
+}
+
+// 7: a limit's result was sized for the whole range: copied (and waited for)
+// into a block of its own size, so what a caller keeps is sized by what it
+// asked for.
+int shrink_truncated(cb_scan* r, hipStream_t s) {
+  size_t o[5];
+  const uint64_t count = r->count, kb = r->key_bytes, vb = r->val_bytes;
+  if (!r->truncated || cb::scan_layout(count, kb, vb, o) * 2 >= r->block_cap) return CB_OK;
+  const cb_scan big = *r;
+  TempBlock old{r->device, big.block, big.block_cap};
+  r->block = nullptr;
+  if (int rc = scan_alloc(r, count, kb, vb)) return rc;
+  HIP_TRY(hipMemcpyAsync(r->key_off, big.key_off, (count + 1) * 8, hipMemcpyDeviceToDevice, s));
+  HIP_TRY(hipMemcpyAsync(r->val_off, big.val_off, (count + 1) * 8, hipMemcpyDeviceToDevice, s));
+  HIP_TRY(hipMemcpyAsync(r->which, big.which, count * 4, hipMemcpyDeviceToDevice, s));
+  if (kb) HIP_TRY(hipMemcpyAsync(r->keys, big.keys, kb, hipMemcpyDeviceToDevice, s));
+  if (vb) HIP_TRY(hipMemcpyAsync(r->vals, big.vals, vb, hipMemcpyDeviceToDevice, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return CB_OK;
+}
+
+// Offsets and bytes of a result into host or device memory (either may be NULL).
+int scan_copy(const cb_scan* r, uint64_t* off_out, const uint64_t* off, uint8_t* out, const uint8_t* bytes,
+              uint64_t nbytes) {
+  if (!r) return fail(CB_EINVAL, "null scan");
+  if (!r->count) {  // an empty result holds no device memory
+    const uint64_t zero = 0;
+    return off_out ? put_bytes((uint8_t*)off_out, &zero, 8) : CB_OK;
+  }
+  DeviceGuard dg(r->device);
+  if (off_out) HIP_TRY(hipMemcpy(off_out, off, (r->count + 1) * 8, hipMemcpyDefault));
+  if (out && nbytes) HIP_TRY(hipMemcpy(out, bytes, nbytes, hipMemcpyDefault));
+  return CB_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// Newest-wins merge (compact.hpp). Every temporary is carved from pool blocks
+// released stream-ordered on return (error returns included: nothing the
+// enqueued work touches is freed under it). The call waits for its own stream
+// after staging the sources (pageable memory), for the survivors' totals (the
+// output is sized from them), for the directory's map and at the end (the
+// zone bounds are host results).
+int cb_tables_compact(const cb_table* const* tables, uint32_t nt, uint64_t m_bits, void* stream,
+                      cb_table** table_out, cb_filter** bloom_out) {
+  if (!table_out) return fail(CB_EINVAL, "null argument");
+  *table_out = nullptr;
+  if (bloom_out) *bloom_out = nullptr;
+  int dev = 0;
+  if (int rc = check_table_list(tables, nt, &dev)) return rc;
+  if (bloom_out && m_bits == 0)  // BloomFilter::insert's `% 0` (src/bloom.rs:36)
+    return fail(CB_EZEROM, "attempt to calculate the remainder with a divisor of zero");
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<cb::CompactSrc> srcs;
+  uint64_t n = 0, kbound = 0;
+  if (int rc = compact_sources(tables, nt, srcs, &n, &kbound)) return rc;
+  int rc = cb_init(dev);
+  if (rc) return rc;
+  DeviceGuard dg(dev);
+  Workspace& ws = workspace(dev, s);  // (registers s: the pool retires blocks behind it)
+  std::unique_ptr<cb_table, int (*)(cb_table*)> t(new cb_table(), cb_table_destroy);
+  std::unique_ptr<cb_filter, int (*)(cb_filter*)> f(nullptr, cb_filter_destroy);
+  t->device = dev;
+  if (bloom_out) {
+    cb_filter* fp = nullptr;
+    if ((rc = cb_filter_create(m_bits, dev, &fp))) return rc;
+    f.reset(fp);
+  }
+  TempBlock tmp{dev}, keys{dev};
+  uint64_t h[3] = {0, 0, 0};  // the survivors' lines, file bytes and key bytes
+  if (n) {
+    Merge mg;
+    KeptKeys k;
+    if ((rc = merge_sources(srcs, n, kbound, tmp, &mg, s, h))) return rc;
+    if ((rc = format_survivors(t.get(), mg, h, keys, &k, s))) return rc;
+    if (h[0] && f) {
+      // 4: BloomFilter::new(m) + insert per kept key (src/sstable.rs:59-63)
+      std::lock_guard<std::mutex> lk(ws.mu);
+      if ((rc = insert_locked(ws, f.get(), k.kb, k.ko, 0, h[0], s))) return rc;
+    }
+    if (h[0] && (rc = finish_compacted(t.get(), mg, k, h, s))) return rc;
+  }
+  // 6: no line survives: the empty file, as cb_sstable_create's n == 0
+  if (!h[0] && (rc = finish_empty_file(t.get(), s))) return rc;
+  if (bloom_out) *bloom_out = f.release();
+  *table_out = t.release();
+  return CB_OK;
+}
+
+// Range scan (scan.hpp): the tables cut to [lo, hi) on the device, the cuts
+// merged as compaction merges whole tables, the survivors' keys and decoded
+// values written into the result. Scratch as in cb_tables_compact: pool blocks
+// released stream-ordered on every return path. The call waits for its own
+// stream after staging the table list (pageable memory) and then three times
+// for a few words, each bound-checked before anything is sized from it: the
+// cuts' totals (the merge's scratch), the survivors' totals (the result), and
+// the kept keys' and values' byte totals at the end (the result is complete
+// when the call returns); a truncated result's copy is one more.
+int cb_tables_scan(const cb_table* const* tables, uint32_t nt, const uint8_t* lo, uint64_t lo_len, const uint8_t* hi,
+                   uint64_t hi_len, int has_hi, uint64_t limit, void* stream, void** out) {
+  if (!out) return fail(CB_EINVAL, "null argument");
+  *out = nullptr;
+  int dev = 0;
+  if (int rc = check_scan_args(tables, nt, lo, lo_len, hi, &hi_len, has_hi, &dev)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  // the non-empty tables, newest first
+  std::vector<cb::ScanTable> tabs;
+  uint64_t all_lines = 0, all_bytes = 0;
+  if (int rc = for_live_tables(tables, nt, [&](cb_table* ti, uint32_t i) {
+        tabs.push_back(cb::ScanTable{ti->data, ti->rec, ti->pfx, ti->fence, ti->llen, ti->nlines, ti->len, i, 0});
+        all_lines += ti->nlines;
+        all_bytes += ti->len;
+      }))
+    return rc;
+  std::unique_ptr<cb_scan, int (*)(void*)> r(new cb_scan(), cb_scan_destroy);
+  r->device = dev;
+  // an empty result: nothing to search (no lines at all, or lo >= hi), no
+  // line inside the range, or none that survives the merge
+  auto done = [&] {
+    *out = r.release();
+    return CB_OK;
+  };
+  if (tabs.empty() || (has_hi && cb::key_cmp(lo, lo_len, hi, hi_len) >= 0)) return done();
+  int rc = cb_init(dev);
+  if (rc) return rc;
+  DeviceGuard dg(dev);
+  (void)workspace(dev, s);  // (registers s: the pool retires blocks behind it)
+  TempBlock cuts{dev}, tmp{dev}, vtmp{dev};
+  ScanCuts c;
+  if ((rc = cut_tables(tabs, all_lines, all_bytes, lo, lo_len, hi, hi_len, has_hi, cuts, s, &c))) return rc;
+  if (!c.n) return done();
+  // 3: compaction's merge over the cuts
+  Merge mg;
+  uint64_t h[3];
+  if ((rc = merge_alloc(0, c.n, c.kbound, tmp, &mg))) return rc;
+  if ((rc = enqueue_merge(mg, c.dsrc, c.nsrc, s, h))) return rc;
+  const uint64_t cnt = h[0], len = h[1], kbytes = h[2];
+  if (len < kbytes + 2 * cnt) return fail(CB_EHIP, "scan: inconsistent totals");
+  if (!cnt) return done();
+  // A kept line is `key \t text \n` and its value decodes to at most 3 bytes
+  // per 4 of text, which bounds the values before any is decoded.
+  const uint64_t count = limit && limit < cnt ? limit : cnt;
+  const uint64_t vcap = (len - kbytes - 2 * cnt) / 4 * 3;
+  ValueSpans v;
+  if ((rc = emit_scan_result(r.get(), mg, c, count, kbytes, vcap, vtmp, s, &v))) return rc;
+  // 5: the read path's value tail
+  if ((rc = enqueue_value_decode(v, count, r->vals, vcap, true, false, s))) return rc;
+  if ((rc = take_scan_totals(r.get(), count, cnt, kbytes, vcap, s))) return rc;
+  if ((rc = shrink_truncated(r.get(), s))) return rc;
+  return done();
+}
+
+int cb_key_prefix_end(const uint8_t* prefix, uint64_t len, uint8_t* out, uint64_t* out_len, int* has_end) {
+  if ((len && (!prefix || !out)) || !out_len || !has_end) return fail(CB_EINVAL, "null argument");
+  *has_end = cb::key_prefix_end(prefix, len, out, out_len) ? 1 : 0;
+  return CB_OK;
+}
+
+int cb_tables_scan_prefix(const cb_table* const* tables, uint32_t nt, const uint8_t* prefix, uint64_t prefix_len,
+                          uint64_t limit, void* stream, void** out) {
+  if (!out) return fail(CB_EINVAL, "null argument");
+  *out = nullptr;
+  if (prefix_len && !prefix) return fail(CB_EINVAL, "null prefix with a length");
+  std::vector<uint8_t> end(prefix_len ? prefix_len : 1);
+  uint64_t end_len = 0;
+  const bool has_end = cb::key_prefix_end(prefix, prefix_len, end.data(), &end_len);
+  return cb_tables_scan(tables, nt, prefix, prefix_len, end.data(), end_len, has_end ? 1 : 0, limit, stream, out);
+}
+
+int cb_scan_info(const void* scan, uint64_t* count, uint64_t* key_bytes, uint64_t* val_bytes, int* truncated) {
+  const cb_scan* r = (const cb_scan*)scan;
+  if (!r) return fail(CB_EINVAL, "null scan");
+  if (count) *count = r->count;
+  if (key_bytes) *key_bytes = r->key_bytes;
+  if (val_bytes) *val_bytes = r->val_bytes;
+  if (truncated) *truncated = r->truncated ? 1 : 0;
+  return CB_OK;
+}
+
+int cb_scan_keys(const void* scan, uint64_t* key_off, uint8_t* keys) {
+  const cb_scan* r = (const cb_scan*)scan;
+  return scan_copy(r, key_off, r ? r->key_off : nullptr, keys, r ? r->keys : nullptr, r ? r->key_bytes : 0);
+}
+
+int cb_scan_values(const void* scan, uint64_t* val_off, uint8_t* vals) {
+  const cb_scan* r = (const cb_scan*)scan;
+  return scan_copy(r, val_off, r ? r->val_off : nullptr, vals, r ? r->vals : nullptr, r ? r->val_bytes : 0);
+}
+
+int cb_scan_which(const void* scan, int32_t* which) {
+  const cb_scan* r = (const cb_scan*)scan;
+  if (!r) return fail(CB_EINVAL, "null scan");
+  if (!r->count || !which) return CB_OK;
+  DeviceGuard dg(r->device);
+  HIP_TRY(hipMemcpy(which, r->which, r->count * 4, hipMemcpyDefault));
+  return CB_OK;
+}
+
+int cb_scan_destroy(void* scan) {
+  cb_scan* r = (cb_scan*)scan;
+  if (!r) return CB_OK;
+  pool_release(r->device, r->block, r->block_cap);
+  delete r;
+  return CB_OK;
+}
+
+}  // extern "C"

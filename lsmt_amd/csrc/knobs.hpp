@@ -16,12 +16,12 @@
 //   CB_POOL_SLAB=0      capi_runtime.cpp: small pool requests get their own blocks
 //   CB_POOL_CONTIG=1    capi_runtime.cpp: pool memory physically contiguous
 //   CB_BUILD_BATCH=n    capi_filter.cpp: filters per batched build launch pair
-//   CB_NO_BUCKETS=1     capi_sstable.cpp: reads without the key buckets
-//   CB_NO_SCREEN=1      capi_sstable.cpp: wide reads without the screen
-//   CB_SCREEN_HBITS=h   capi_sstable.cpp: the wide screen's hash bits (0..8)
-//   CB_WIDE_MAPS=0      capi_sstable.cpp: wide reads find the maps through the views
-//   CB_DECODE_RAW=0     capi_sstable.cpp: always the k_tile_scan launch before the decode
-//   CB_BIN_T=t          capi_sstable.cpp: bin-sort group target (0: no bin sort)
+//   CB_NO_BUCKETS=1     capi_get.cpp: reads without the key buckets
+//   CB_NO_SCREEN=1      capi_get.cpp: wide reads without the screen
+//   CB_SCREEN_HBITS=h   capi_get.cpp: the wide screen's hash bits (0..8)
+//   CB_WIDE_MAPS=0      capi_get.cpp: wide reads find the maps through the views
+//   CB_DECODE_RAW=0     capi_get.cpp: always the k_tile_scan launch before the decode (gets and scans)
+//   CB_BIN_T=t          capi_flush.cpp: bin-sort group target (0: no bin sort)
 //   CB_ORDER_FENCE=1    comm.cpp: the order event with its system-scope fence
 //   CB_BUILD_TB=b       tileplan.cpp plan_build: tile bits
 //   CB_BUILD_KPT=k      tileplan.cpp plan_build: partition keys per thread (1, 2, 4)

@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "hash.hpp"
+#include "tablehost.hpp"
 #include "zone.hpp"
 
 namespace cb {
@@ -34,16 +35,8 @@ struct WideZone {
   uint32_t any;
 };
 
-// How a group of up to 64 tables (newest first, t0 .. t0 + gn - 1) maps to
-// the set's slots, so the kernel can take the group's candidate bits from a
-// window of the rows instead of one bit per table:
-//   kind 0: slot(t0 + i) = lo + i          (ascending)
-//   kind 1: slot(t0 + i) = lo + gn - 1 - i (descending: the LSM's age order,
-//           slot = position in Vec<SsTable>, walked with .rev())
-//   kind 2: any other mapping, one bit read per table (slots[t0 + i]).
-struct WideGroup {
-  uint32_t kind, lo, gn, pad;
-};
+// (WideGroup, how a group of up to 64 tables maps to the set's slots, is in
+// tablehost.hpp with the host code that classifies the groups.)
 
 // slots 0..nf-1 := the packed filters fw[0..nf-1] (device array of nf word
 // pointers, all of size m); slots nf..W-1 zero.

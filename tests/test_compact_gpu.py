@@ -346,6 +346,29 @@ def test_refusals(gpu):
     assert t.data() == good.data()
 
 
+def test_refusal_precedence(gpu):
+    """Which refusal wins when a call earns several, straight through the ABI:
+    the list's own checks, then m == 0, then the tables' contents."""
+    import ctypes
+    L = gpu._lib.load()
+    good = gpu.Table(oracle.sstable_create([(b"a", b"1"), (b"b", b"2")]))
+    unsorted = gpu.Table(raw_file([(b"b", b64(b"1")), (b"a", b64(b"2"))]))
+    assert not unsorted.well_formed
+
+    def compact(handles, nt, m_bits):
+        th, fh = ctypes.c_void_p(0xdead), ctypes.c_void_p(0xbeef)
+        arr = ctypes.cast((ctypes.c_void_p * 2)(*handles), ctypes.c_void_p)
+        rc = L.cb_tables_compact(arr, nt, m_bits, None, ctypes.byref(th), ctypes.byref(fh))
+        assert not th.value and not fh.value
+        return rc, L.cb_last_error().decode()
+
+    assert compact([good._h.value, None], 2, 0) == (CB_EINVAL, "null table")
+    rc, msg = compact([good._h.value, unsorted._h.value], 2, 0)
+    assert rc == gpu._lib.CB_EZEROM and msg == "attempt to calculate the remainder with a divisor of zero"
+    assert compact([good._h.value, unsorted._h.value], 2, 1024) == (CB_EINVAL, "an input table is not well-formed")
+    assert compact([good._h.value, None], 0, 0) == (CB_EINVAL, "no tables")
+
+
 # ---- lifetime -----------------------------------------------------------------------
 
 def test_pending_inputs_and_inputs_destroyed_at_once(gpu):

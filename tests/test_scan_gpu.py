@@ -499,3 +499,80 @@ def test_refusals(gpu):
     assert L.cb_tables_scan(arr, 1, b"", 0, None, 7, 0, 0, None, ctypes.byref(out)) == 0
     r = gpu.ScanResult(out.value, 0)
     assert r.items() == [(b"a", b"1"), (b"b", b"2")] and r.which().tolist() == [0, 0]
+
+
+def test_refusal_precedence(gpu):
+    """Which refusal wins when a call earns several, straight through the ABI:
+    the list's own checks, then the bounds, then the tables' contents."""
+    L = gpu._lib.load()
+    good = gpu.Table(oracle.sstable_create([(b"a", b"1"), (b"b", b"2")]))
+    unsorted = gpu.Table(raw_file([(b"b", b64(b"1")), (b"a", b64(b"2"))]))
+    assert not unsorted.well_formed
+
+    def scan(handles, nt, lo, lo_len):
+        out = ctypes.c_void_p(0xDEAD)
+        arr = ctypes.cast((ctypes.c_void_p * 2)(*handles), ctypes.c_void_p)
+        rc = L.cb_tables_scan(arr, nt, lo, lo_len, None, 0, 0, 0, None, ctypes.byref(out))
+        assert not out.value
+        return rc, L.cb_last_error().decode()
+
+    assert scan([good._h.value, None], 2, None, 1) == (CB_EINVAL, "null table")
+    assert scan([good._h.value, None], 1, None, 1) == (CB_EINVAL, "null lower bound with a length")
+    assert scan([good._h.value, unsorted._h.value], 2, None, 1) == (CB_EINVAL, "null lower bound with a length")
+    assert scan([good._h.value, unsorted._h.value], 2, b"", 0) == (CB_EINVAL, "an input table is not well-formed")
+    assert scan([good._h.value, None], 0, None, 1) == (CB_EINVAL, "no tables")
+
+
+# ---- the value tail shared with the gets --------------------------------------------
+
+def test_results_on_each_side_of_the_raw_decode_limit(gpu):
+    """262145 results are one more than the decode scans the tile sums for
+    itself (sstable.hpp decode_raw_max): the full scan takes the one-block
+    scan ahead of the decode, the scan limited to 262144 the decode alone, on
+    the same data. The expectation is built here from the lists the file is
+    written from."""
+    n = 262145
+    keys = [b"%08d" % i for i in range(n)]
+    vals = [b"" if i % 7 == 0 else bytes([i % 251]) for i in range(n)]
+    table = gpu.Table(b"".join(k + b"\t" + b64(v) + b"\n" for k, v in zip(keys, vals)))
+    assert table.well_formed and table.nlines == n
+    want = [(k, v, 0) for k, v in zip(keys, vals)]
+    assert_result(gpu.scan([table]), want, False, "full")
+    assert_result(gpu.scan([table], limit=n - 1), want[:n - 1], True, "limit 262144")
+
+
+def test_get_scan_get_on_one_stream(gpu):
+    """A get of 65 keys over two tables, a scan of the same tables and the get
+    again, enqueued on one stream with device outputs: the scan's value tail
+    has buffers of its own, so both gets answer as the oracle does."""
+    import torch
+    rng = np.random.default_rng(41)
+    pool = hex_keys(rng, 2200)
+    per = [pool[:900], pool[600:1800]]  # 300 keys in both tables
+    files = [oracle.sstable_create([(k, named(t, k[:7])) for k in ks]) for t, ks in enumerate(per)]
+    tables = open_tables(gpu, files)
+    look = np.frombuffer(b"".join(pool[:20] + pool[600:620] + pool[1700:1720] + pool[-5:]), np.uint8).reshape(-1, 16)
+    assert len(look) == 65
+    d = np.ascontiguousarray(look.reshape(-1))
+    offs = np.arange(0, 16 * (len(look) + 1), 16, dtype=np.uint64)
+    ow, ovoff, ovals = oracle.get_many([oracle.OracleTable(f) for f in files], None, d, offs)
+    assert (ow >= 0).sum() >= 60
+    dk = gpu.DeviceKeys(torch.from_numpy(look.copy()).cuda())
+    s = torch.cuda.Stream()
+
+    def get():
+        o = (torch.empty(65, dtype=torch.int32, device="cuda"), torch.empty(66, dtype=torch.int64, device="cuda"),
+             torch.zeros(len(ovals) + 64, dtype=torch.uint8, device="cuda"))
+        assert gpu.get_many(tables, dk, out=o, stream=s, wait=False)[2] is None
+        return o
+    first = get()
+    ref = Ref(files)
+    r, want = check(gpu, ref, tables, stream=s)
+    assert r.count == len(ref.entries) > 1200
+    second = get()
+    s.synchronize()
+    for w, vo, vb in (first, second):
+        assert np.array_equal(w.cpu().numpy(), ow)
+        assert np.array_equal(vo.cpu().numpy().view(np.uint64), ovoff)
+        assert vb[:len(ovals)].cpu().numpy().tobytes() == ovals
+    assert all(torch.equal(a, b) for a, b in zip(first, second))

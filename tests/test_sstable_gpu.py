@@ -835,7 +835,7 @@ def _walk_expect(dicts, look):
 def test_get_many_table_and_row_uploads_follow_the_call(gpu):
     """The workspace keeps what it last uploaded (the tables' views, their
     rows / slots) and uploads again only when a call's differ
-    (capi_sstable.cpp upload_if_changed): a stale copy would answer from the
+    (capi_get.cpp upload_if_changed): a stale copy would answer from the
     wrong table or gate without any error. One stream, five calls in a row
     through the hit-row form and through a width-32 FilterSet: list A, a list
     B of the same length with one table replaced, A again, A with permuted

@@ -189,7 +189,7 @@ def format_blocks(lines):
 
 def format_stage(lines):
     """The stage launch_format picks: cap_bytes / n * 256 * 5 / 4 against 16 KiB
-    (capi_sstable.cpp: cap_bytes = K + 2n + (4V + 8n) / 3 + 17)."""
+    (tablehost.hpp flush_file_bound: K + 2n + (4V + 8n) / 3 + 17)."""
     n = len(lines)
     K, V = sum(kl for kl, _ in lines), sum(vl for _, vl in lines)
     cap = K + 2 * n + (4 * V + 8 * n) // 3 + 17

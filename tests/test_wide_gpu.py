@@ -234,7 +234,7 @@ def test_wide_get_many_348_tables(gpu, lsm300, mapping):
 def test_wide_get_many_groups_follow_the_slots(gpu):
     """The wide walk's per-call host data (the groups of 64 tables and how
     each maps to slots, the screen, the maps' copy) is kept in the workspace
-    and replaced only when a call's differs (capi_sstable.cpp
+    and replaced only when a call's differs (capi_get.cpp
     upload_if_changed / rebuild_if_changed): stale groups would read the
     wrong slots' bits without any error. One stream, the same 65 tables (two
     groups) of 3 lines four times in a row: slots ascending, descending,
