@@ -386,6 +386,49 @@ int cb_tables_scan(const cb_table* const* tables, uint32_t nt, const uint8_t* lo
  * it from the returned keys is the caller's (src/lib.rs:184). */
 int cb_tables_scan_prefix(const cb_table* const* tables, uint32_t nt, const uint8_t* prefix, uint64_t prefix_len,
                           uint64_t limit, void* stream, void** out /* cb_scan */);
+/* Many ranges in one call: the result holds the entries of
+ * cb_tables_scan(tables, lo_r, hi_r, limit = 0) for r = 0, 1, ... one after the
+ * other (keys, values and which exactly as those nr calls return them), from
+ * one merge instead of nr, and cb_scan_ranges says where each range's entries
+ * begin. The ranges must ascend and be pairwise disjoint, in Rust's `Ord for
+ * [u8]` (bytes, then length): for every r < nr - 1, lo_r <= lo_{r+1} and
+ * hi_r <= lo_{r+1}, and only the last range may be unbounded above. A range
+ * with lo_r >= hi_r is legal and empty; touching ranges (hi_r == lo_{r+1}) are
+ * legal, a key equal to that bound belonging to the later one. The whole
+ * result is therefore sorted by key bytes too. Overlapping ranges, ranges in
+ * descending order and nested prefixes ("a:" with "a:b:") are refused: every
+ * range's cut of a table is one source of the one sort, a line inside two
+ * ranges would stand in two sources, and the merge's select, which keeps one
+ * line per run of equal keys, would fold the copies into one entry. Sorting
+ * the ranges and splitting them at overlaps is the caller's.
+ * There is no limit in this form (a per-range limit needs ranks within a
+ * range, which the merge does not compute); cb_tables_scan keeps its limit.
+ * ranges: range r = [ bounds[bound_off[2r] .. bound_off[2r+1]),
+ *                     bounds[bound_off[2r+1] .. bound_off[2r+2]) );
+ * bound_off: 2*nr+1 non-decreasing host uint64. last_unbounded != 0: the last
+ * range has no upper bound (its hi bytes are ignored).
+ * Everything else is as for cb_tables_scan. CB_EINVAL (nothing returned,
+ * *out = NULL, nothing enqueued): out NULL, cb_tables_scan's table-list
+ * errors, nr == 0, bound_off NULL, bounds NULL with a non-zero total,
+ * bound_off that decreases, ranges that break the ordering rule, and more
+ * than 65536 cuts (nr * the number of tables with lines: one block of the
+ * device walks the cuts). */
+int cb_tables_scan_many(const cb_table* const* tables, uint32_t nt, const uint8_t* bounds,
+                        const uint64_t* bound_off, uint32_t nr, int last_unbounded,
+                        void* stream, void** out /* cb_scan */);
+/* cb_tables_scan_many over prefixes: prefix r = prefixes[prefix_off[r] ..
+ * prefix_off[r+1]) (prefix_off: np+1 non-decreasing host uint64); range r =
+ * [p_r, cb_key_prefix_end(p_r)). A prefix without an end (empty, all 0xFF) is
+ * legal only as the last one. Database::scan_ns over many namespaces is the
+ * prefixes ns_r + ":" in ascending order; a namespace that starts with
+ * another's prefix ("a" and "a:b") nests and takes a call of its own. */
+int cb_tables_scan_prefixes(const cb_table* const* tables, uint32_t nt, const uint8_t* prefixes,
+                            const uint64_t* prefix_off, uint32_t np, void* stream, void** out /* cb_scan */);
+/* Where each range's entries lie: range r's are [range_off[r], range_off[r+1]),
+ * range_off[0] = 0, range_off[nr] = count. range_off: nr+1 host uint64
+ * (nullable); *nr (nullable) = the number of ranges. A result of
+ * cb_tables_scan / _prefix reports nr = 1, {0, count}. Host only. */
+int cb_scan_ranges(const void* r, uint64_t* nr, uint64_t* range_off);
 /* Host only, no device: the exclusive upper bound of "starts with prefix",
  * i.e. the prefix without its trailing 0xFF bytes and its last remaining byte
  * incremented (*out_len <= len bytes into out). *has_end = 0, *out_len = 0

@@ -862,6 +862,9 @@ class ScanResult:
         check(_L().cb_scan_info(self._h, ctypes.byref(n), ctypes.byref(kb), ctypes.byref(vb), ctypes.byref(tr)))
         self.count, self.key_bytes, self.val_bytes = int(n.value), int(kb.value), int(vb.value)
         self.truncated = bool(tr.value)
+        nr = ctypes.c_uint64()
+        check(_L().cb_scan_ranges(self._h, ctypes.byref(nr), None))
+        self.nranges = int(nr.value)
 
     def close(self) -> None:
         if getattr(self, "_h", None) and self._h.value:
@@ -922,6 +925,13 @@ class ScanResult:
     def items(self) -> "list[tuple[bytes, bytes]]":
         return list(zip(self.keys(), self.values()))
 
+    def range_off(self) -> np.ndarray:
+        """uint64[nranges + 1]: range r's entries are [range_off[r],
+        range_off[r + 1]) (cb_scan_ranges; {0, count} for a scan of one range)."""
+        off = np.zeros(self.nranges + 1, np.uint64)
+        check(_L().cb_scan_ranges(self._h, None, _ptr_of(off)[0]))
+        return off
+
 
 def scan(tables: Sequence[Table], lo=b"", hi=None, prefix=None, limit: int = 0, stream=None) -> ScanResult:
     """Every live entry of well-formed tables (tables[0] newest, as get_many
@@ -951,6 +961,48 @@ def scan(tables: Sequence[Table], lo=b"", hi=None, prefix=None, limit: int = 0, 
         hi_b = _key_bytes(hi) if hi is not None else None
         _raise(_L().cb_tables_scan(arr, len(tables), lo_b, len(lo_b), hi_b, len(hi_b) if hi_b is not None else 0,
                                    int(hi_b is not None), int(limit), _stream(stream), ctypes.byref(h)))
+    return ScanResult(h.value, dev)
+
+
+def scan_many(tables: Sequence[Table], ranges=None, prefixes=None, stream=None) -> ScanResult:
+    """Many scans from one merge (cb_tables_scan_many / _prefixes): the entries
+    of scan(tables, lo, hi) for every (lo, hi) of `ranges`, or of scan(tables,
+    prefix=p) for every p of `prefixes`, one after the other in one
+    ScanResult, whose range_off() says where each begins (so len of range r,
+    COUNT(*) per namespace, is a difference of two offsets). The ranges must
+    ascend and be pairwise disjoint (each lo and hi <= the next lo; touching
+    is fine, empty ranges are fine); overlapping, descending or nested ones
+    ("a:" with "a:b:") are refused (CB_EINVAL): sort them, split them at
+    overlaps, or fall back to single scans. hi=None (unbounded above) is
+    allowed on the last range only, as is a prefix without an end (empty, all
+    0xFF). There is no limit in this form. scan_ns over many namespaces is
+    prefixes=[ns + ":" for ns in sorted(names)]."""
+    if (ranges is None) == (prefixes is None):
+        raise ValueError("exactly one of ranges and prefixes")
+    if not tables:
+        arr, dev = None, 0
+    else:
+        arr = ctypes.cast((ctypes.c_void_p * len(tables))(*[t._h.value for t in tables]), ctypes.c_void_p)
+        dev = tables[0].device
+    h = ctypes.c_void_p()
+    if prefixes is not None:
+        parts = [_key_bytes(p) for p in prefixes]
+        last_unbounded = 0
+    else:
+        pairs = [(_key_bytes(lo), hi) for lo, hi in ranges]
+        if any(hi is None for _, hi in pairs[:-1]):
+            raise ValueError("hi=None is allowed on the last range only")
+        last_unbounded = int(bool(pairs) and pairs[-1][1] is None)
+        parts = [b for lo, hi in pairs for b in (lo, _key_bytes(hi) if hi is not None else b"")]
+    off = np.zeros(len(parts) + 1, np.uint64)
+    np.cumsum([len(b) for b in parts], out=off[1:])
+    data = b"".join(parts)
+    if prefixes is not None:
+        _raise(_L().cb_tables_scan_prefixes(arr, len(tables), data, _ptr_of(off)[0], len(parts), _stream(stream),
+                                            ctypes.byref(h)))
+    else:
+        _raise(_L().cb_tables_scan_many(arr, len(tables), data, _ptr_of(off)[0], len(parts) // 2, last_unbounded,
+                                        _stream(stream), ctypes.byref(h)))
     return ScanResult(h.value, dev)
 
 

@@ -221,11 +221,13 @@ struct cb_table {
 
 // A scan's result (cb_tables_scan): one pool block holding key_off | val_off
 // | which | keys | vals, complete when the call returns. An empty result has
-// no block.
+// no block. range_off (host): where each range's entries begin, nr + 1
+// offsets for the nr ranges of the call ({0, count} for a scan of one range).
 struct cb_scan {
   int device = 0;
   uint64_t count = 0, key_bytes = 0, val_bytes = 0;
   bool truncated = false;
+  std::vector<uint64_t> range_off;
   void* block = nullptr;
   size_t block_cap = 0;
   uint64_t *key_off = nullptr, *val_off = nullptr;  // count + 1 entries each

@@ -1,7 +1,8 @@
 // capi_merge.cpp — merging SSTables on the device: the newest-wins merge
 // (compact.hpp) and its two users, compaction into one new table
-// (cb_tables_compact) and range and prefix scans into a result
-// (cb_tables_scan, scan.hpp), with the result's accessors (cb_scan_*).
+// (cb_tables_compact) and range and prefix scans, of one range or of many
+// disjoint ones in one merge, into a result (cb_tables_scan*, scan.hpp), with
+// the result's accessors (cb_scan_*).
 //
 // Reference: src/sstable.rs:51-98 (the file a compaction writes),
 // src/lib.rs:125-146 (Database::get, whose answers both reproduce).
@@ -211,18 +212,41 @@ int scan_alloc(cb_scan* r, uint64_t count, uint64_t kb, uint64_t vb) {
   return CB_OK;
 }
 
-// ---- cb_tables_scan's steps, in the order it takes them ----
+// ---- the scan's steps, in the order scan_ranges takes them ----
+
+// The ranges of one call (host memory, keyrange.hpp's list, already checked
+// against its ordering rule): range r = [lo(r), hi(r)), the last one without
+// a hi when last_unbounded.
+struct RangeList {
+  const uint8_t* bounds;
+  const uint64_t* off;  // 2 nr + 1
+  uint32_t nr;
+  bool last_unbounded;
+  const uint8_t* lo(uint32_t r) const { return bounds + off[2 * r]; }
+  uint64_t lo_len(uint32_t r) const { return off[2 * r + 1] - off[2 * r]; }
+  bool has_hi(uint32_t r) const { return r + 1 < nr || !last_unbounded; }
+  const uint8_t* hi(uint32_t r) const { return bounds + off[2 * r + 1]; }
+  uint64_t hi_len(uint32_t r) const { return has_hi(r) ? off[2 * r + 2] - off[2 * r + 1] : 0; }
+  bool empty(uint32_t r) const { return has_hi(r) && cb::key_cmp(lo(r), lo_len(r), hi(r), hi_len(r)) >= 0; }
+};
+
+// The most cuts (ranges x non-empty tables) of one batched call:
+// k_scan_sources is one block that walks them 256 at a time. (cb_tables_scan
+// has no cap: its cuts are its tables.)
+constexpr uint64_t kScanMaxCuts = 65536;
 
 // What step 2 leaves on the device for the merge and the emit (in the call's
 // `cuts` block), and the cuts' totals.
 struct ScanCuts {
   const cb::CompactSrc* dsrc = nullptr;  // the cuts as the merge's sources
   const uint32_t* dmap = nullptr;        // each source's place in the caller's list
-  uint64_t n = 0, kbound = 0;            // lines inside the range, a bound on their keys' bytes
+  const uint32_t* drng = nullptr;        // each source's range
+  uint64_t n = 0, kbound = 0;            // lines inside the ranges, a bound on their keys' bytes
   uint32_t nsrc = 0;
 };
 
-// 1: the arguments: the list, then the bounds (without has_hi, hi is ignored).
+// 1: the arguments of a scan of one range: the list, then the bounds (without
+// has_hi, hi is ignored).
 int check_scan_args(const cb_table* const* tables, uint32_t nt, const uint8_t* lo, uint64_t lo_len, const uint8_t* hi,
                     uint64_t* hi_len, int has_hi, int* dev) {
   if (int rc = check_table_list(tables, nt, dev)) return rc;
@@ -232,71 +256,96 @@ int check_scan_args(const cb_table* const* tables, uint32_t nt, const uint8_t* l
   return CB_OK;
 }
 
-// 2: every table's cut, and the cuts as the merge's sources. Two waits: after
-// staging the tables and the bounds (pageable memory), and for the cuts'
-// totals, checked against the tables' (all_lines, all_bytes) before anything
-// is sized from them.
-int cut_tables(const std::vector<cb::ScanTable>& tabs, uint64_t all_lines, uint64_t all_bytes, const uint8_t* lo,
-               uint64_t lo_len, const uint8_t* hi, uint64_t hi_len, int has_hi, TempBlock& cuts, hipStream_t s,
-               ScanCuts* out) {
-  const uint32_t ntab = (uint32_t)tabs.size();
+// 2: every table's cut to every range, and the cuts as the merge's sources.
+// Two waits: after staging the tables, the ranges and their bounds (pageable
+// memory), and for the cuts' totals, checked against the tables' (all_lines,
+// all_bytes: the ranges are disjoint, so a table's cuts share no line) before
+// anything is sized from them.
+int cut_tables(const std::vector<cb::ScanTable>& tabs, uint64_t all_lines, uint64_t all_bytes, const RangeList& rl,
+               TempBlock& cuts, hipStream_t s, ScanCuts* out) {
+  const uint32_t ntab = (uint32_t)tabs.size(), nr = rl.nr;
+  const uint64_t ncut = (uint64_t)ntab * nr, at0 = rl.off[0], nbytes = rl.off[2 * (uint64_t)nr] - at0;
   cb::Carver c;
-  const size_t o_tab = c.take(ntab * sizeof(cb::ScanTable)), o_bnd = c.take(lo_len + hi_len + 16);
-  const size_t up_bytes = c.total();  // (the two parts staged from the host)
-  const size_t o_cut = c.take(ntab * sizeof(cb::ScanCut)), o_src = c.take(ntab * sizeof(cb::CompactSrc)),
-               o_map = c.take(ntab * 4), o_ctot = c.take(3 * 8);
+  const size_t o_tab = c.take(ntab * sizeof(cb::ScanTable)), o_rng = c.take(nr * sizeof(cb::ScanRange)),
+               o_bnd = c.take(nbytes + 16);
+  const size_t up_bytes = c.total();  // (the three parts staged from the host)
+  const size_t o_cut = c.take(ncut * sizeof(cb::ScanCut)), o_src = c.take(ncut * sizeof(cb::CompactSrc)),
+               o_map = c.take(ncut * 4), o_rmap = c.take(ncut * 4), o_ctot = c.take(3 * 8);
   if (int rc = cuts.alloc(c, "device allocation failed for a scan's cuts")) return rc;
   std::vector<uint8_t> up(up_bytes, 0);
   std::memcpy(&up[o_tab], tabs.data(), ntab * sizeof(cb::ScanTable));
-  if (lo_len) std::memcpy(&up[o_bnd], lo, lo_len);
-  if (hi_len) std::memcpy(&up[o_bnd + lo_len], hi, hi_len);
+  cb::ScanRange* hr = (cb::ScanRange*)&up[o_rng];
+  for (uint32_t r = 0; r < nr; ++r) {
+    const uint64_t lo_at = rl.off[2 * r] - at0;
+    hr[r] = cb::ScanRange{lo_at, rl.lo_len(r), lo_at + rl.lo_len(r), rl.hi_len(r), rl.has_hi(r) ? 1u : 0u, 0};
+    if (rl.lo_len(r)) std::memcpy(&up[o_bnd + lo_at], rl.lo(r), rl.lo_len(r));
+    if (rl.hi_len(r)) std::memcpy(&up[o_bnd + hr[r].hi_at], rl.hi(r), rl.hi_len(r));
+  }
   HIP_TRY(hipMemcpyAsync(cuts.p, up.data(), up_bytes, hipMemcpyHostToDevice, s));
   HIP_TRY(hipStreamSynchronize(s));  // the source is pageable
   const cb::ScanTable* dtab = (const cb::ScanTable*)cuts.at(o_tab);
   cb::ScanCut* dcut = (cb::ScanCut*)cuts.at(o_cut);
   cb::CompactSrc* dsrc = (cb::CompactSrc*)cuts.at(o_src);
-  uint32_t* dmap = (uint32_t*)cuts.at(o_map);
+  uint32_t *dmap = (uint32_t*)cuts.at(o_map), *drng = (uint32_t*)cuts.at(o_rmap);
   uint64_t* dctot = (uint64_t*)cuts.at(o_ctot);
-  const cb::ScanRange range{cuts.at(o_bnd), lo_len, lo_len, hi_len, has_hi ? 1u : 0u, 0};
-  HIP_TRY(cb::launch_scan_bounds(dtab, ntab, range, dcut, s));
-  HIP_TRY(cb::launch_scan_sources(dtab, dcut, ntab, dsrc, dmap, dctot, s));
+  HIP_TRY(cb::launch_scan_bounds(dtab, ntab, (const cb::ScanRange*)cuts.at(o_rng), nr, cuts.at(o_bnd), dcut, s));
+  HIP_TRY(cb::launch_scan_sources(dtab, dcut, ntab, nr, dsrc, dmap, drng, dctot, s));
   uint64_t t[3] = {0, 0, 0};
   HIP_TRY(hipMemcpyAsync(t, dctot, sizeof t, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   const uint64_t n = t[0], kbound = t[1], nsrc = t[2];
-  if (n > all_lines || kbound > all_bytes || nsrc > ntab || nsrc > n || (n && !nsrc))
+  if (n > all_lines || kbound > all_bytes || nsrc > ncut || nsrc > n || (n && !nsrc))
     return fail(CB_EHIP, "scan: inconsistent cut totals");
   if (n > 0xFFFFFFFFull) return fail(CB_EINVAL, "too many lines inside the range for one scan");
-  *out = ScanCuts{dsrc, dmap, n, kbound, (uint32_t)nsrc};
+  *out = ScanCuts{dsrc, dmap, drng, n, kbound, (uint32_t)nsrc};
   return CB_OK;
 }
 
 // 4: the result's block for `count` entries (room for kbytes key bytes and
 // vcap value bytes) and, in it, the kept keys, their offsets and sources;
-// the kept values' spans go into v, scratch in vtmp, for the decode.
-int emit_scan_result(cb_scan* r, const Merge& mg, const ScanCuts& c, uint64_t count, uint64_t kbytes, uint64_t vcap,
-                     TempBlock& vtmp, hipStream_t s, ValueSpans* v) {
+// the kept values' spans go into v, scratch in vtmp, for the decode. A scan
+// of many ranges (nr > 1; count is then every survivor) also gets the
+// entries' ranges and, from them, where each range begins (*droff, nr + 1
+// offsets in vtmp).
+int emit_scan_result(cb_scan* r, const Merge& mg, const ScanCuts& c, uint32_t nr, uint64_t count, uint64_t kbytes,
+                     uint64_t vcap, TempBlock& vtmp, hipStream_t s, ValueSpans* v, const uint64_t** droff) {
   if (int rc = scan_alloc(r, count, kbytes, vcap)) return rc;
   const uint64_t vtiles = cb::get_tiles(count);
   cb::Carver vc;
-  const size_t o_vsrc = vc.take(count * 8), o_dlen = vc.take(count * 8), o_vsum = vc.take(vtiles * 8);
+  const size_t o_vsrc = vc.take(count * 8), o_dlen = vc.take(count * 8), o_vsum = vc.take(vtiles * 8),
+               o_rid = vc.take(nr > 1 ? count * 4 : 0), o_roff = vc.take(nr > 1 ? (nr + 1ull) * 8 : 0);
   if (int rc = vtmp.alloc(vc, "device allocation failed for a scan's value spans")) return rc;
   uint64_t *vsrc = (uint64_t*)vtmp.at(o_vsrc), *dlen = (uint64_t*)vtmp.at(o_dlen), *vsum = (uint64_t*)vtmp.at(o_vsum);
+  uint32_t* rid = nr > 1 ? (uint32_t*)vtmp.at(o_rid) : nullptr;
   HIP_TRY(hipMemsetAsync(vsum, 0, vtiles * 8, s));
-  HIP_TRY(cb::launch_scan_emit(mg.order, mg.side, mg.slen, mg.tcnt, mg.tkeys, mg.tot, c.dsrc, c.dmap, c.nsrc, mg.n,
-                               count, r->keys, r->key_off, r->which, vsrc, dlen, vsum, s));
+  HIP_TRY(cb::launch_scan_emit(mg.order, mg.side, mg.slen, mg.tcnt, mg.tkeys, mg.tot, c.dsrc, c.dmap, c.drng, c.nsrc,
+                               mg.n, count, r->keys, r->key_off, r->which, rid, vsrc, dlen, vsum, s));
+  *droff = nullptr;
+  if (nr > 1) {
+    uint64_t* roff = (uint64_t*)vtmp.at(o_roff);
+    HIP_TRY(cb::launch_scan_range_off(rid, count, nr, roff, s));
+    *droff = roff;
+  }
   *v = ValueSpans{vsrc, dlen, vsum, r->val_off};
   return CB_OK;
 }
 
-// 6: the kept keys' and values' byte totals (one wait: the result is complete
-// when the call returns), checked against what the block was sized for.
-int take_scan_totals(cb_scan* r, uint64_t count, uint64_t cnt, uint64_t kbytes, uint64_t vcap, hipStream_t s) {
+// 6: the kept keys' and values' byte totals and, for a scan of many ranges,
+// the ranges' offsets (droff) (one wait: the result is complete when the call
+// returns), checked against what the block was sized for.
+int take_scan_totals(cb_scan* r, uint64_t count, uint64_t cnt, uint64_t kbytes, uint64_t vcap, const uint64_t* droff,
+                     hipStream_t s) {
   uint64_t e[2] = {0, 0};
+  std::vector<uint64_t>& ro = r->range_off;
   HIP_TRY(hipMemcpyAsync(&e[0], r->key_off + count, 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipMemcpyAsync(&e[1], r->val_off + count, 8, hipMemcpyDeviceToHost, s));
+  if (droff) HIP_TRY(hipMemcpyAsync(ro.data(), droff, ro.size() * 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   if (e[0] > kbytes || e[1] > vcap) return fail(CB_EHIP, "scan: inconsistent result totals");
+  if (!droff) ro.back() = count;
+  bool ok = ro.front() == 0 && ro.back() == count;
+  for (size_t i = 0; ok && i + 1 < ro.size(); ++i) ok = ro[i] <= ro[i + 1];
+  if (!ok) return fail(CB_EHIP, "scan: inconsistent range offsets");
   r->count = count;
   r->key_bytes = e[0];
   r->val_bytes = e[1];
@@ -336,6 +385,75 @@ int scan_copy(const cb_scan* r, uint64_t* off_out, const uint64_t* off, uint8_t*
   if (off_out) HIP_TRY(hipMemcpy(off_out, off, (r->count + 1) * 8, hipMemcpyDefault));
   if (out && nbytes) HIP_TRY(hipMemcpy(out, bytes, nbytes, hipMemcpyDefault));
   return CB_OK;
+}
+
+// ---- the scan itself ----
+
+// Range scans (scan.hpp): the tables cut to every range on the device, the
+// cuts merged as compaction merges whole tables, the survivors' keys and
+// decoded values written into the result. One implementation: a scan of one
+// range (cb_tables_scan, with its limit) is its nr = 1 case and skips the
+// entries' ranges and their offsets. Scratch as in cb_tables_compact: pool
+// blocks released stream-ordered on every return path. The call waits for its
+// own stream after staging the table list (pageable memory) and then three
+// times for a few words, each bound-checked before anything is sized from it:
+// the cuts' totals (the merge's scratch), the survivors' totals (the result),
+// and the kept keys' and values' byte totals at the end, with the ranges'
+// offsets (the result is complete when the call returns); a truncated
+// result's copy is one more.
+int scan_ranges(const cb_table* const* tables, uint32_t nt, int dev, const RangeList& rl, uint64_t max_cuts,
+                uint64_t limit, hipStream_t s, void** out) {
+  // the non-empty tables, newest first
+  std::vector<cb::ScanTable> tabs;
+  uint64_t all_lines = 0, all_bytes = 0;
+  if (int rc = for_live_tables(tables, nt, [&](cb_table* ti, uint32_t i) {
+        tabs.push_back(cb::ScanTable{ti->data, ti->rec, ti->pfx, ti->fence, ti->llen, ti->nlines, ti->len, i, 0});
+        all_lines += ti->nlines;
+        all_bytes += ti->len;
+      }))
+    return rc;
+  if (max_cuts && (uint64_t)rl.nr * tabs.size() > max_cuts)
+    return fail(CB_EINVAL, "too many cuts (ranges x non-empty tables) for one scan");
+  std::unique_ptr<cb_scan, int (*)(void*)> r(new cb_scan(), cb_scan_destroy);
+  r->device = dev;
+  r->range_off.assign(rl.nr + 1ull, 0);
+  // an empty result: nothing to search (no lines at all, or lo >= hi in every
+  // range), no line inside any range, or none that survives the merge
+  auto done = [&] {
+    *out = r.release();
+    return CB_OK;
+  };
+  bool all_empty = true;
+  for (uint32_t i = 0; all_empty && i < rl.nr; ++i) all_empty = rl.empty(i);
+  if (tabs.empty() || all_empty) return done();
+  int rc = cb_init(dev);
+  if (rc) return rc;
+  DeviceGuard dg(dev);
+  (void)workspace(dev, s);  // (registers s: the pool retires blocks behind it)
+  TempBlock cuts{dev}, tmp{dev}, vtmp{dev};
+  ScanCuts c;
+  if ((rc = cut_tables(tabs, all_lines, all_bytes, rl, cuts, s, &c))) return rc;
+  if (!c.n) return done();
+  // 3: compaction's merge over the cuts
+  Merge mg;
+  uint64_t h[3];
+  if ((rc = merge_alloc(0, c.n, c.kbound, tmp, &mg))) return rc;
+  if ((rc = enqueue_merge(mg, c.dsrc, c.nsrc, s, h))) return rc;
+  const uint64_t cnt = h[0], len = h[1], kbytes = h[2];
+  if (len < kbytes + 2 * cnt) return fail(CB_EHIP, "scan: inconsistent totals");
+  if (!cnt) return done();
+  // A kept line is `key \t text \n` and its value decodes to at most 3 bytes
+  // per 4 of text, which bounds the values before any is decoded.
+  const uint64_t count = limit && limit < cnt ? limit : cnt;
+  const uint64_t vcap = (len - kbytes - 2 * cnt) / 4 * 3;
+  ValueSpans v;
+  const uint64_t* droff = nullptr;
+  if ((rc = emit_scan_result(r.get(), mg, c, rl.nr, count, kbytes, vcap, vtmp, s, &v, &droff))) return rc;
+  // 5: the read path's value tail
+  if ((rc = enqueue_value_decode(v, count, r->vals, vcap, true, false, s))) return rc;
+  if ((rc = take_scan_totals(r.get(), count, cnt, kbytes, vcap, droff, s))) return rc;
+  if ((rc = shrink_truncated(r.get(), s))) return rc;
+  return done();
 }
 
 }  // namespace
@@ -394,67 +512,57 @@ int cb_tables_compact(const cb_table* const* tables, uint32_t nt, uint64_t m_bit
   return CB_OK;
 }
 
-// Range scan (scan.hpp): the tables cut to [lo, hi) on the device, the cuts
-// merged as compaction merges whole tables, the survivors' keys and decoded
-// values written into the result. Scratch as in cb_tables_compact: pool blocks
-// released stream-ordered on every return path. The call waits for its own
-// stream after staging the table list (pageable memory) and then three times
-// for a few words, each bound-checked before anything is sized from it: the
-// cuts' totals (the merge's scratch), the survivors' totals (the result), and
-// the kept keys' and values' byte totals at the end (the result is complete
-// when the call returns); a truncated result's copy is one more.
 int cb_tables_scan(const cb_table* const* tables, uint32_t nt, const uint8_t* lo, uint64_t lo_len, const uint8_t* hi,
                    uint64_t hi_len, int has_hi, uint64_t limit, void* stream, void** out) {
   if (!out) return fail(CB_EINVAL, "null argument");
   *out = nullptr;
   int dev = 0;
   if (int rc = check_scan_args(tables, nt, lo, lo_len, hi, &hi_len, has_hi, &dev)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  // the non-empty tables, newest first
-  std::vector<cb::ScanTable> tabs;
-  uint64_t all_lines = 0, all_bytes = 0;
-  if (int rc = for_live_tables(tables, nt, [&](cb_table* ti, uint32_t i) {
-        tabs.push_back(cb::ScanTable{ti->data, ti->rec, ti->pfx, ti->fence, ti->llen, ti->nlines, ti->len, i, 0});
-        all_lines += ti->nlines;
-        all_bytes += ti->len;
-      }))
-    return rc;
-  std::unique_ptr<cb_scan, int (*)(void*)> r(new cb_scan(), cb_scan_destroy);
-  r->device = dev;
-  // an empty result: nothing to search (no lines at all, or lo >= hi), no
-  // line inside the range, or none that survives the merge
-  auto done = [&] {
-    *out = r.release();
-    return CB_OK;
-  };
-  if (tabs.empty() || (has_hi && cb::key_cmp(lo, lo_len, hi, hi_len) >= 0)) return done();
-  int rc = cb_init(dev);
-  if (rc) return rc;
-  DeviceGuard dg(dev);
-  (void)workspace(dev, s);  // (registers s: the pool retires blocks behind it)
-  TempBlock cuts{dev}, tmp{dev}, vtmp{dev};
-  ScanCuts c;
-  if ((rc = cut_tables(tabs, all_lines, all_bytes, lo, lo_len, hi, hi_len, has_hi, cuts, s, &c))) return rc;
-  if (!c.n) return done();
-  // 3: compaction's merge over the cuts
-  Merge mg;
-  uint64_t h[3];
-  if ((rc = merge_alloc(0, c.n, c.kbound, tmp, &mg))) return rc;
-  if ((rc = enqueue_merge(mg, c.dsrc, c.nsrc, s, h))) return rc;
-  const uint64_t cnt = h[0], len = h[1], kbytes = h[2];
-  if (len < kbytes + 2 * cnt) return fail(CB_EHIP, "scan: inconsistent totals");
-  if (!cnt) return done();
-  // A kept line is `key \t text \n` and its value decodes to at most 3 bytes
-  // per 4 of text, which bounds the values before any is decoded.
-  const uint64_t count = limit && limit < cnt ? limit : cnt;
-  const uint64_t vcap = (len - kbytes - 2 * cnt) / 4 * 3;
-  ValueSpans v;
-  if ((rc = emit_scan_result(r.get(), mg, c, count, kbytes, vcap, vtmp, s, &v))) return rc;
-  // 5: the read path's value tail
-  if ((rc = enqueue_value_decode(v, count, r->vals, vcap, true, false, s))) return rc;
-  if ((rc = take_scan_totals(r.get(), count, cnt, kbytes, vcap, s))) return rc;
-  if ((rc = shrink_truncated(r.get(), s))) return rc;
-  return done();
+  // the list of one range: lo's bytes, then hi's
+  std::vector<uint8_t> bounds(lo_len + hi_len);
+  if (lo_len) std::memcpy(bounds.data(), lo, lo_len);
+  if (hi_len) std::memcpy(bounds.data() + lo_len, hi, hi_len);
+  const uint64_t off[3] = {0, lo_len, lo_len + hi_len};
+  return scan_ranges(tables, nt, dev, RangeList{bounds.data(), off, 1, !has_hi}, 0, limit, (hipStream_t)stream, out);
+}
+
+int cb_tables_scan_many(const cb_table* const* tables, uint32_t nt, const uint8_t* bounds, const uint64_t* bound_off,
+                        uint32_t nr, int last_unbounded, void* stream, void** out) {
+  if (!out) return fail(CB_EINVAL, "null argument");
+  *out = nullptr;
+  int dev = 0;
+  if (int rc = check_table_list(tables, nt, &dev)) return rc;
+  if (!nr) return fail(CB_EINVAL, "no ranges");
+  if (!bound_off) return fail(CB_EINVAL, "null bound offsets");
+  if (!bounds)  // no byte may be read: every offset is the first, or the list is refused
+    for (uint64_t i = 1; i <= 2ull * nr; ++i)
+      if (bound_off[i] != bound_off[0]) return fail(CB_EINVAL, "null bounds with a non-zero total");
+  if (cb::range_list_first_bad(bounds, bound_off, nr, last_unbounded != 0) >= 0)
+    return fail(CB_EINVAL, "the ranges are not ascending and disjoint (or their offsets decrease)");
+  return scan_ranges(tables, nt, dev, RangeList{bounds, bound_off, nr, last_unbounded != 0}, kScanMaxCuts, 0,
+                     (hipStream_t)stream, out);
+}
+
+int cb_tables_scan_prefixes(const cb_table* const* tables, uint32_t nt, const uint8_t* prefixes,
+                            const uint64_t* prefix_off, uint32_t np, void* stream, void** out) {
+  if (!out) return fail(CB_EINVAL, "null argument");
+  *out = nullptr;
+  int dev = 0;
+  if (int rc = check_table_list(tables, nt, &dev)) return rc;
+  if (!np) return fail(CB_EINVAL, "no prefixes");
+  if (!prefix_off) return fail(CB_EINVAL, "null prefix offsets");
+  if (!prefixes)
+    for (uint64_t i = 1; i <= np; ++i)
+      if (prefix_off[i] != prefix_off[0]) return fail(CB_EINVAL, "null prefixes with a non-zero total");
+  std::vector<uint8_t> bounds;
+  std::vector<uint64_t> off;
+  bool last_unbounded = false;
+  if (cb::prefix_list_to_ranges(prefixes, prefix_off, np, bounds, off, &last_unbounded) >= 0)
+    return fail(CB_EINVAL, "a prefix without an end before the last one (or prefix offsets that decrease)");
+  if (cb::range_list_first_bad(bounds.data(), off.data(), np, last_unbounded) >= 0)
+    return fail(CB_EINVAL, "the prefixes are not ascending and disjoint");
+  return scan_ranges(tables, nt, dev, RangeList{bounds.data(), off.data(), np, last_unbounded}, kScanMaxCuts, 0,
+                     (hipStream_t)stream, out);
 }
 
 int cb_key_prefix_end(const uint8_t* prefix, uint64_t len, uint8_t* out, uint64_t* out_len, int* has_end) {
@@ -472,6 +580,14 @@ int cb_tables_scan_prefix(const cb_table* const* tables, uint32_t nt, const uint
   uint64_t end_len = 0;
   const bool has_end = cb::key_prefix_end(prefix, prefix_len, end.data(), &end_len);
   return cb_tables_scan(tables, nt, prefix, prefix_len, end.data(), end_len, has_end ? 1 : 0, limit, stream, out);
+}
+
+int cb_scan_ranges(const void* scan, uint64_t* nr, uint64_t* range_off) {
+  const cb_scan* r = (const cb_scan*)scan;
+  if (!r) return fail(CB_EINVAL, "null scan");
+  if (nr) *nr = r->range_off.size() - 1;
+  if (range_off) std::memcpy(range_off, r->range_off.data(), r->range_off.size() * 8);
+  return CB_OK;
 }
 
 int cb_scan_info(const void* scan, uint64_t* count, uint64_t* key_bytes, uint64_t* val_bytes, int* truncated) {

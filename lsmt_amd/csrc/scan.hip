@@ -2,23 +2,27 @@
 // the range, hand the cuts to compaction's merge as its sources, and emit the
 // survivors' keys, sources and value spans.
 //
-//   k_scan_bounds — sixteen lanes per (table, bound): the lower bound of the
-//       bound's zero-padded 8-byte prefix down the table's fence levels, each
+//   k_scan_bounds — sixteen lanes per (range, table, bound): the lower bound
+//       of the bound's zero-padded 8-byte prefix down the table's fence levels, each
 //       level one run of at most 16 entries read by the sixteen lanes at once
 //       (one 128-B line, one round trip per level where a bisection takes
 //       four), then the lines that share the prefix by record compares, again
 //       sixteen probes a round. A lower-bound search: it never asks whether
-//       the bound is a key of the table. The searches are few (two per table)
-//       and each is a short chain of dependent loads, so the kernel is as
-//       long as one table's descent.
+//       the bound is a key of the table. Each search is a short chain of
+//       dependent loads and all run side by side (two per table and range),
+//       so the kernel is as long as one table's descent.
 //   k_scan_sources — one block: the scan of the cuts' lengths, the non-empty
-//       cuts packed as CompactSrc entries (rec + first, llen + first).
+//       cuts packed as CompactSrc entries (rec + first, llen + first), each
+//       with its table's place in the caller's list and its range.
 //   k_scan_emit — one block per tile of sorted records, as k_compact_format:
 //       the survivors' ranks and key offsets from the scanned tile sums and a
 //       block scan, the tile's key bytes assembled into aligned dwords, and
 //       per survivor its key offset, source and value span. A tile's
 //       survivors lie in at most two of the decode's tiles, so the block adds
-//       two partial sums of their decoded lengths.
+//       two partial sums of their decoded lengths. For a scan of many ranges
+//       it also writes each survivor's range.
+//   k_scan_range_off — one lane per range: where its entries begin, the lower
+//       bound of its number in the survivors' ranges (they ascend with the keys).
 #include <hip/hip_runtime.h>
 
 #include "blockscan.hpp"
@@ -88,20 +92,25 @@ __device__ __forceinline__ uint64_t group_bound(const TableView& v, const Query&
   return group_lower_bound(i0, e, sub, [&](uint64_t l) { return rec_cmp(v, grec(v.rec, l), q) < 0; });
 }
 
-__global__ __launch_bounds__(kNT) void k_scan_bounds(const ScanTable* __restrict__ tab, uint32_t nt, ScanRange range,
-                                                     ScanCut* __restrict__ cut) {
+__global__ __launch_bounds__(kNT) void k_scan_bounds(const ScanTable* __restrict__ tab, uint32_t nt,
+                                                     const ScanRange* __restrict__ rng, uint32_t nr,
+                                                     const uint8_t* __restrict__ bytes, ScanCut* __restrict__ cut) {
   const uint32_t sub = threadIdx.x & (kGroup - 1);
-  const uint64_t nq = 2ull * nt;  // search 2 t: table t's lo, 2 t + 1: its hi
+  // search 2 c: cut c's lo, 2 c + 1: its hi (adjacent groups of one wave);
+  // cut c = r * nt + t: range r of table t
+  const uint64_t nq = 2ull * nt * nr;
   uint64_t g = ((uint64_t)blockIdx.x * kNT + threadIdx.x) / kGroup;
   const bool live = g < nq;
   if (!live) g = nq - 1;  // (the last groups repeat the last search: every lane stays in step)
-  const uint32_t t = (uint32_t)(g >> 1);
+  const uint64_t c_at = g >> 1;
+  const uint32_t t = (uint32_t)(c_at % nt);
   const bool upper = g & 1;
   const ScanTable st = tab[t];
+  const ScanRange range = rng[c_at / nt];
   const TableView v =
       make_view(st.data, st.rec, st.pfx, st.fence, st.nlines, fence_levels(st.nlines), true, nullptr, nullptr);
   Query q;
-  q.p = range.bytes + (upper ? range.hi_at : 0);
+  q.p = bytes + (upper ? range.hi_at : range.lo_at);
   q.len = upper ? range.hi_len : range.lo_len;
   q.w0 = be_chunk(q.p, q.len < 8 ? q.len : 8);
   q.w1 = q.len > 8 ? be_chunk(q.p + 8, q.len - 8 < 8 ? q.len - 8 : 8) : 0;
@@ -114,27 +123,30 @@ __global__ __launch_bounds__(kNT) void k_scan_bounds(const ScanTable* __restrict
     c.last = hi_b > b ? hi_b : b;  // lo >= hi: an empty cut
     const uint64_t end = c.last < st.nlines ? grec(st.rec, c.last).start : st.len;
     c.bytes = c.last > c.first ? end - grec(st.rec, c.first).start : 0;
-    cut[t] = c;
+    cut[c_at] = c;
   }
 }
 
 __global__ __launch_bounds__(kNT) void k_scan_sources(const ScanTable* __restrict__ tab,
-                                                      const ScanCut* __restrict__ cut, uint32_t nt,
+                                                      const ScanCut* __restrict__ cut, uint32_t nt, uint32_t nr,
                                                       CompactSrc* __restrict__ src, uint32_t* __restrict__ src_tab,
+                                                      uint32_t* __restrict__ src_rng,
                                                       uint64_t* __restrict__ totals) {
+  const uint32_t ncut = nt * nr;  // (the host caps the cuts of a call)
   uint64_t base = 0, bytes = 0, ns = 0;
-  for (uint32_t t0 = 0; t0 < nt; t0 += kNT) {
-    const uint32_t t = t0 + threadIdx.x;
+  for (uint32_t c0 = 0; c0 < ncut; c0 += kNT) {
+    const uint32_t ci = c0 + threadIdx.x;
     ScanCut c{0, 0, 0};
-    if (t < nt) c = cut[t];
+    if (ci < ncut) c = cut[ci];
     const uint64_t len = c.last - c.first;
     uint64_t tl, tn, tb, unused;
     const uint64_t off = block_scan<(int)kNT>(len, &tl);
     const uint64_t si = block_scan_sum2<(int)kNT>(len ? 1 : 0, c.bytes, 0, &tn, &tb, &unused);
     if (len) {
-      const ScanTable st = tab[t];
+      const ScanTable st = tab[ci % nt];
       src[ns + si] = CompactSrc{st.data, st.rec + c.first, st.llen + c.first, base + off};
       src_tab[ns + si] = st.index;
+      src_rng[ns + si] = ci / nt;
     }
     base += tl;
     bytes += tb;
@@ -154,10 +166,12 @@ __global__ __launch_bounds__(kNT) void k_scan_emit(const SortKey* __restrict__ o
                                                    const uint64_t* __restrict__ tkeys,
                                                    const uint64_t* __restrict__ totals,
                                                    const CompactSrc* __restrict__ src,
-                                                   const uint32_t* __restrict__ src_tab, uint32_t nsrc, uint64_t n,
+                                                   const uint32_t* __restrict__ src_tab,
+                                                   const uint32_t* __restrict__ src_rng, uint32_t nsrc, uint64_t n,
                                                    uint64_t count, uint8_t* __restrict__ keys,
                                                    uint64_t* __restrict__ key_off, int32_t* __restrict__ which,
-                                                   uint64_t* __restrict__ vsrc, uint64_t* __restrict__ dlen,
+                                                   uint32_t* __restrict__ rid, uint64_t* __restrict__ vsrc,
+                                                   uint64_t* __restrict__ dlen,
                                                    uint64_t* __restrict__ vsum) {
   __shared__ uint64_t s_off[kNT + 1];    // survivor i's first key byte in the tile
   __shared__ const uint8_t* s_src[kNT];  // its key
@@ -192,7 +206,9 @@ __global__ __launch_bounds__(kNT) void k_scan_emit(const SortKey* __restrict__ o
     if (r <= count) key_off[r] = tkeys[blockIdx.x] + kof;
   }
   if (out) {
-    which[r] = (int32_t)src_tab[src_of(src, nsrc, g)];
+    const uint32_t si = src_of(src, nsrc, g);
+    which[r] = (int32_t)src_tab[si];
+    if (rid) rid[r] = src_rng[si];  // (uniform: a scan of many ranges)
     vsrc[r] = (uint64_t)(uintptr_t)(sd.src + sd.klen + 1);
     dlen[r] = sd.vdl;
   }
@@ -227,32 +243,55 @@ __global__ __launch_bounds__(kNT) void k_scan_emit(const SortKey* __restrict__ o
   if (tail0 + threadIdx.x < tl) o[tail0 + threadIdx.x] = (uint8_t)byte_at(key_of(tail0 + threadIdx.x), tail0 + threadIdx.x);
 }
 
+// One lane per r in [0, nr]: the first entry of the non-decreasing rid[0..count)
+// that is >= r.
+__global__ __launch_bounds__(kNT) void k_scan_range_off(const uint32_t* __restrict__ rid, uint64_t count, uint32_t nr,
+                                                        uint64_t* __restrict__ range_off) {
+  const uint64_t r = (uint64_t)blockIdx.x * kNT + threadIdx.x;
+  if (r > nr) return;
+  uint64_t lo = 0, hi = count;  // rid[i] < r for i < lo, rid[i] >= r for i >= hi
+  while (lo < hi) {
+    const uint64_t mid = lo + (hi - lo) / 2;
+    if (rid[mid] < r) lo = mid + 1;
+    else hi = mid;
+  }
+  range_off[r] = lo;
+}
+
 }  // namespace
 
-hipError_t launch_scan_bounds(const ScanTable* tab, uint32_t nt, const ScanRange& range, ScanCut* cut,
-                              hipStream_t s) {
-  if (!nt) return hipSuccess;
+hipError_t launch_scan_bounds(const ScanTable* tab, uint32_t nt, const ScanRange* rng, uint32_t nr,
+                              const uint8_t* bytes, ScanCut* cut, hipStream_t s) {
+  if (!nt || !nr) return hipSuccess;
   ProfScope ps("k_scan_bounds", s);
-  hipLaunchKernelGGL(k_scan_bounds, dim3(blocks_for(2ull * nt * kGroup, kNT)), dim3(kNT), 0, s, tab, nt, range, cut);
+  hipLaunchKernelGGL(k_scan_bounds, dim3(blocks_for(2ull * nt * nr * kGroup, kNT)), dim3(kNT), 0, s, tab, nt, rng, nr,
+                     bytes, cut);
   return hipGetLastError();
 }
 
-hipError_t launch_scan_sources(const ScanTable* tab, const ScanCut* cut, uint32_t nt, CompactSrc* src,
-                               uint32_t* src_tab, uint64_t* totals, hipStream_t s) {
+hipError_t launch_scan_sources(const ScanTable* tab, const ScanCut* cut, uint32_t nt, uint32_t nr, CompactSrc* src,
+                               uint32_t* src_tab, uint32_t* src_rng, uint64_t* totals, hipStream_t s) {
   ProfScope ps("k_scan_sources", s);
-  hipLaunchKernelGGL(k_scan_sources, dim3(1), dim3(kNT), 0, s, tab, cut, nt, src, src_tab, totals);
+  hipLaunchKernelGGL(k_scan_sources, dim3(1), dim3(kNT), 0, s, tab, cut, nt, nr, src, src_tab, src_rng, totals);
   return hipGetLastError();
 }
 
 hipError_t launch_scan_emit(const SortKey* order, const CompactSide* side, const uint64_t* slen,
                             const uint64_t* tcnt, const uint64_t* tkeys, const uint64_t* totals,
-                            const CompactSrc* src, const uint32_t* src_tab, uint32_t nsrc, uint64_t n, uint64_t count,
-                            uint8_t* keys, uint64_t* key_off, int32_t* which, uint64_t* vsrc, uint64_t* dlen,
-                            uint64_t* vsum, hipStream_t s) {
+                            const CompactSrc* src, const uint32_t* src_tab, const uint32_t* src_rng, uint32_t nsrc,
+                            uint64_t n, uint64_t count, uint8_t* keys, uint64_t* key_off, int32_t* which,
+                            uint32_t* rid, uint64_t* vsrc, uint64_t* dlen, uint64_t* vsum, hipStream_t s) {
   if (!n || !count) return hipSuccess;
   ProfScope ps("k_scan_emit", s);
   hipLaunchKernelGGL(k_scan_emit, dim3(blocks_for(n, kNT)), dim3(kNT), 0, s, order, side, slen, tcnt, tkeys, totals,
-                     src, src_tab, nsrc, n, count, keys, key_off, which, vsrc, dlen, vsum);
+                     src, src_tab, src_rng, nsrc, n, count, keys, key_off, which, rid, vsrc, dlen, vsum);
+  return hipGetLastError();
+}
+
+hipError_t launch_scan_range_off(const uint32_t* rid, uint64_t count, uint32_t nr, uint64_t* range_off, hipStream_t s) {
+  ProfScope ps("k_scan_range_off", s);
+  hipLaunchKernelGGL(k_scan_range_off, dim3(blocks_for((uint64_t)nr + 1, kNT)), dim3(kNT), 0, s, rid, count, nr,
+                     range_off);
   return hipGetLastError();
 }
 
