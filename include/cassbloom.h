@@ -424,6 +424,61 @@ int cb_tables_scan_many(const cb_table* const* tables, uint32_t nt, const uint8_
  * another's prefix ("a" and "a:b") nests and takes a call of its own. */
 int cb_tables_scan_prefixes(const cb_table* const* tables, uint32_t nt, const uint8_t* prefixes,
                             const uint64_t* prefix_off, uint32_t np, void* stream, void** out /* cb_scan */);
+/* ---- live rows: tombstones in the tables -----------------------------------
+ * The reference deletes a row by writing a tombstone: exec_delete inserts the
+ * 8-byte timestamp with an empty payload (src/query.rs:240-261), and every
+ * reader of a scan (SELECT COUNT(*), the schema-less select, SHOW TABLES)
+ * does `let (_, data) = split_ts(&bytes); if data.is_empty() { continue; }`
+ * (src/query.rs:21-27, 343-346, 395-398). split_ts returns the bytes
+ * themselves below 8 and strips 8 from there on, so a decoded value of length
+ * L is DEAD exactly when L == 0 or L == 8. A value that does not decode is
+ * neither live nor dead: such a line is no entry at all, as everywhere above.
+ * A tombstone SHADOWS AND IS THEN DROPPED: Database::get stops at the newest
+ * line that decodes, tombstone or not, so a key's fate is decided by that
+ * line alone. If it is dead the key is absent from live results, even when
+ * an older table holds a live value for it; no older value ever comes back.
+ * The three entries below apply that rule to the tables; cb_tables_scan*,
+ * cb_tables_compact and cb_get_many_* are unchanged and still return
+ * tombstones as entries. The memtable's own tombstones are the store's, which
+ * merges its memtable over these results as it does for get.
+ * Range lists are cb_tables_scan_many's (bounds, bound_off, nr,
+ * last_unbounded): the same format, ordering rule, cut cap and refusals; a
+ * caller builds prefix bounds with cb_key_prefix_end. All three check their
+ * own arguments (outputs, range list, limit, m_bits) before they look at the
+ * table list, so with two errors at once they report the argument's. */
+/* Counts without a result: entries[r] = the number of entries
+ * cb_tables_scan(tables, lo_r, hi_r, limit = 0) returns, live[r] = how many of
+ * them are not dead: SELECT COUNT(*) of a namespace (src/query.rs:341-357) is
+ * live[r] for the prefix ns + ":". entries, live: host arrays of nr uint64,
+ * either may be NULL, not both. The call runs the scan's cuts and merge up to
+ * its select and then counts: it allocates no result, copies no key and
+ * decodes no value. It waits for its own stream (one wait fewer than a
+ * scan); the counts are complete on return. nr == 0 is legal and counts
+ * nothing; no table with lines, or lo >= hi in every range: zeros, without
+ * touching the device. CB_EINVAL: both arrays NULL (nothing written); else
+ * the arrays are zeroed first and cb_tables_scan_many's refusals apply. */
+int cb_tables_count(const cb_table* const* tables, uint32_t nt, const uint8_t* bounds,
+                    const uint64_t* bound_off, uint32_t nr, int last_unbounded, void* stream,
+                    uint64_t* entries /* nr, nullable */, uint64_t* live /* nr, nullable */);
+/* cb_tables_scan_many's result without the dead entries (the cb_scan_*
+ * accessors are unchanged; cb_scan_ranges' offsets count live entries).
+ * limit > 0 is legal with nr == 1 only (CB_EINVAL otherwise): the first
+ * `limit` live entries, `truncated` saying whether more live entries
+ * qualified. Everything else, refusals included, as cb_tables_scan_many. */
+int cb_tables_scan_live(const cb_table* const* tables, uint32_t nt, const uint8_t* bounds,
+                        const uint64_t* bound_off, uint32_t nr, int last_unbounded, uint64_t limit,
+                        void* stream, void** out /* cb_scan */);
+/* cb_tables_compact's contract with the set narrowed to
+ *   entries = { (k, Database::get(k)) : k in K, get(k) is Some and not dead }:
+ * the file, line index, Bloom filter and zone bounds are exactly what
+ * cb_tables_compact would produce from those entries; nothing live gives the
+ * empty file. THE CALLER'S RULE: it is correct only when no older table of
+ * the store stays outside the list (a full compaction). A dropped tombstone
+ * can no longer shadow, so an older table left out would bring its deleted
+ * rows back. The library cannot check this. Arguments, errors and waits as
+ * cb_tables_compact; without tombstones in the inputs it does the same work. */
+int cb_tables_compact_live(const cb_table* const* tables, uint32_t nt, uint64_t m_bits, void* stream,
+                           cb_table** table_out, cb_filter** bloom_out /* nullable */);
 /* Where each range's entries lie: range r's are [range_off[r], range_off[r+1]),
  * range_off[0] = 0, range_off[nr] = count. range_off: nr+1 host uint64
  * (nullable); *nr (nullable) = the number of ranges. A result of

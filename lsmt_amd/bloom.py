@@ -1006,6 +1006,82 @@ def scan_many(tables: Sequence[Table], ranges=None, prefixes=None, stream=None) 
     return ScanResult(h.value, dev)
 
 
+def _range_list(ranges, prefixes):
+    """(bounds bytes, bound_off uint64[2 nr + 1], nr, last_unbounded) of a
+    list of (lo, hi) ranges, or of prefixes turned into ranges with
+    prefix_end: cb_tables_scan_many's list format."""
+    if (ranges is None) == (prefixes is None):
+        raise ValueError("exactly one of ranges and prefixes")
+    if prefixes is not None:
+        ranges = [(p, prefix_end(p)) for p in map(_key_bytes, prefixes)]
+    pairs = [(_key_bytes(lo), hi) for lo, hi in ranges]
+    if any(hi is None for _, hi in pairs[:-1]):
+        raise ValueError("hi=None (or a prefix without an end) is allowed on the last range only")
+    last_unbounded = int(bool(pairs) and pairs[-1][1] is None)
+    parts = [b for lo, hi in pairs for b in (lo, _key_bytes(hi) if hi is not None else b"")]
+    off = np.zeros(len(parts) + 1, np.uint64)
+    np.cumsum([len(b) for b in parts], out=off[1:])
+    return b"".join(parts), off, len(pairs), last_unbounded
+
+
+def _table_list(tables: Sequence[Table]):
+    if not tables:
+        return None, 0
+    return ctypes.cast((ctypes.c_void_p * len(tables))(*[t._h.value for t in tables]), ctypes.c_void_p), tables[0].device
+
+
+def count(tables: Sequence[Table], ranges=None, prefixes=None, stream=None):
+    """Per range, how many entries scan_many(tables, ...) would return and how
+    many of them are live rows, without building a result (cb_tables_count):
+    (entries, live), two uint64 arrays. A value is dead when the reference's
+    split_ts (src/query.rs:21-27) leaves no payload, the tombstone exec_delete
+    writes (src/query.rs:240-261); a key whose newest decodable line is dead
+    counts in entries and not in live, whatever older tables hold. SELECT
+    COUNT(*) per namespace (src/query.rs:341-357) is live for
+    prefixes=[ns + ":" for ns in sorted(names)]. Ranges as scan_many takes
+    them; prefixes become ranges through prefix_end."""
+    data, off, nr, last_unbounded = _range_list(ranges, prefixes)
+    arr, _ = _table_list(tables)
+    entries, live = np.zeros(max(nr, 1), np.uint64), np.zeros(max(nr, 1), np.uint64)
+    _raise(_L().cb_tables_count(arr, len(tables), data, _ptr_of(off)[0], nr, last_unbounded, _stream(stream),
+                                _ptr_of(entries)[0], _ptr_of(live)[0]))
+    return entries[:nr], live[:nr]
+
+
+def scan_live(tables: Sequence[Table], ranges=None, prefixes=None, limit: int = 0, stream=None) -> ScanResult:
+    """scan_many without the dead entries (cb_tables_scan_live): deleted rows
+    (count's rule) are left out on the device, and range_off() counts live
+    entries. A tombstone shadows before it is dropped: a key whose newest
+    decodable line is dead is absent even when an older table holds a live
+    value. limit > 0 takes exactly one range: the first `limit` live entries,
+    ScanResult.truncated saying whether more live entries qualified."""
+    data, off, nr, last_unbounded = _range_list(ranges, prefixes)
+    arr, dev = _table_list(tables)
+    h = ctypes.c_void_p()
+    _raise(_L().cb_tables_scan_live(arr, len(tables), data, _ptr_of(off)[0], nr, last_unbounded, int(limit),
+                                    _stream(stream), ctypes.byref(h)))
+    return ScanResult(h.value, dev)
+
+
+def compact_live(tables: Sequence[Table], m: int = 1024, stream=None):
+    """compact() that also drops deleted rows (cb_tables_compact_live): the
+    merged table holds every key whose newest decodable line is not a
+    tombstone (count's rule), and the Bloom filter and zone map are of those
+    keys. Correct only for a full compaction: with an older table of the store
+    left out of `tables`, a dropped tombstone no longer shadows that table's
+    line and the deleted row comes back. Returns (Table, BloomFilter, ZoneMap)
+    as compact does."""
+    arr, dev = _table_list(tables)
+    th, fh = ctypes.c_void_p(), ctypes.c_void_p()
+    _raise(_L().cb_tables_compact_live(arr, len(tables), int(m), _stream(stream), ctypes.byref(th), ctypes.byref(fh)))
+    table = Table._adopt(th.value, dev)
+    bloom = BloomFilter(0, device=dev, _handle=fh.value)
+    zone = ZoneMap()
+    if table.nlines:
+        zone = ZoneMap(table._zone(0), table._zone(1))
+    return table, bloom, zone
+
+
 def _to_var(b: KeyBatch) -> KeyBatch:
     keys = np.ascontiguousarray(b.keys)
     offs = (np.arange(0, b.key_len * (b.n + 1), b.key_len, dtype=np.uint64) if b.key_len

@@ -2,7 +2,10 @@
 // (compact.hpp) and its two users, compaction into one new table
 // (cb_tables_compact) and range and prefix scans, of one range or of many
 // disjoint ones in one merge, into a result (cb_tables_scan*, scan.hpp), with
-// the result's accessors (cb_scan_*).
+// the result's accessors (cb_scan_*). The live-row entries run the same steps:
+// cb_tables_compact_live and cb_tables_scan_live with the select that drops
+// tombstones (liverow.hpp), cb_tables_count with the plain select and a
+// counting kernel in place of the scan's tail.
 //
 // Reference: src/sstable.rs:51-98 (the file a compaction writes),
 // src/lib.rs:125-146 (Database::get, whose answers both reproduce).
@@ -90,10 +93,10 @@ int merge_alloc(uint32_t nsrc_cap, uint64_t n, uint64_t kbound, TempBlock& tmp, 
   return CB_OK;
 }
 // The merge of sources dsrc[0..nsrc) (device, m.n lines in all) on s, up to
-// the survivors' totals h = {lines, file bytes, key bytes}: read back (they
-// size the caller's output), the stream waited for, and checked against the
-// inputs' bounds before anything is sized from them.
-int enqueue_merge(const Merge& m, const cb::CompactSrc* dsrc, uint32_t nsrc, hipStream_t s, uint64_t (&h)[3]) {
+// and including the select (nothing is waited for): the sorted order and, per
+// sorted record, whether it survives (slen) with the tiles' sums. drop_dead:
+// the live-row entries' select, which keeps no tombstone (liverow.hpp).
+int enqueue_merge_select(const Merge& m, const cb::CompactSrc* dsrc, uint32_t nsrc, bool drop_dead, hipStream_t s) {
   const uint64_t n = m.n;
   HIP_TRY(cb::launch_compact_klen(dsrc, nsrc, n, m.klen, s));
   HIP_TRY(cb::launch_scan_u64(m.klen, m.ko, n, m.scan, s));
@@ -104,7 +107,18 @@ int enqueue_merge(const Merge& m, const cb::CompactSrc* dsrc, uint32_t nsrc, hip
   // the stable sort by key, input index last: a key's lines leave it
   // adjacent, newest first
   if (int rc = enqueue_key_sort(m.plan, m.kb, m.ko, n, m.order, m.sort, m.dr, s, nullptr, nullptr, nullptr)) return rc;
-  HIP_TRY(cb::launch_compact_select(m.order, m.side, m.kb, m.ko, n, m.slen, m.tcnt, m.tbytes, m.tkeys, s));
+  HIP_TRY(cb::launch_compact_select(m.order, m.side, m.kb, m.ko, n, drop_dead, m.slen, m.tcnt, m.tbytes, m.tkeys, s));
+  return CB_OK;
+}
+// The rest of the merge for a caller that writes the survivors out: the scans
+// of the tile sums and the survivors' totals h = {lines, file bytes, key
+// bytes}, read back (they size the caller's output), the stream waited for,
+// and checked against the inputs' bounds before anything is sized from them.
+// (A count stops at the select: it places no survivor.)
+int enqueue_merge(const Merge& m, const cb::CompactSrc* dsrc, uint32_t nsrc, bool drop_dead, hipStream_t s,
+                  uint64_t (&h)[3]) {
+  const uint64_t n = m.n;
+  if (int rc = enqueue_merge_select(m, dsrc, nsrc, drop_dead, s)) return rc;
   HIP_TRY(cb::launch_tile_scan(m.tcnt, m.tiles, m.tot + 0, s));
   HIP_TRY(cb::launch_tile_scan(m.tbytes, m.tiles, m.tot + 1, s));
   HIP_TRY(cb::launch_tile_scan(m.tkeys, m.tiles, m.tot + 2, s));
@@ -139,13 +153,13 @@ int compact_sources(const cb_table* const* tables, uint32_t nt, std::vector<cb::
 
 // 2: the merge over the sources, staged into its scratch (one wait: the
 // source is pageable), up to the survivors' totals h (enqueue_merge's wait).
-int merge_sources(const std::vector<cb::CompactSrc>& srcs, uint64_t n, uint64_t kbound, TempBlock& tmp, Merge* mg,
-                  hipStream_t s, uint64_t (&h)[3]) {
+int merge_sources(const std::vector<cb::CompactSrc>& srcs, uint64_t n, uint64_t kbound, bool drop_dead,
+                  TempBlock& tmp, Merge* mg, hipStream_t s, uint64_t (&h)[3]) {
   const uint32_t nsrc = (uint32_t)srcs.size();
   if (int rc = merge_alloc(nsrc, n, kbound, tmp, mg)) return rc;
   HIP_TRY(hipMemcpyAsync(mg->dsrc, srcs.data(), nsrc * sizeof(cb::CompactSrc), hipMemcpyHostToDevice, s));
   HIP_TRY(hipStreamSynchronize(s));  // the source is pageable
-  return enqueue_merge(*mg, mg->dsrc, nsrc, s, h);
+  return enqueue_merge(*mg, mg->dsrc, nsrc, drop_dead, s, h);
 }
 
 // 3: the survivors (h = {lines, file bytes, key bytes}) formatted into t: the
@@ -253,6 +267,42 @@ int check_scan_args(const cb_table* const* tables, uint32_t nt, const uint8_t* l
   if (lo_len && !lo) return fail(CB_EINVAL, "null lower bound with a length");
   if (!has_hi) *hi_len = 0;
   if (*hi_len && !hi) return fail(CB_EINVAL, "null upper bound with a length");
+  return CB_OK;
+}
+
+// The list of a batched call (cb_tables_scan_many's format and ordering rule,
+// keyrange.hpp), shared by every entry that takes one.
+int check_range_list(const uint8_t* bounds, const uint64_t* bound_off, uint32_t nr, int last_unbounded) {
+  if (!nr) return fail(CB_EINVAL, "no ranges");
+  if (!bound_off) return fail(CB_EINVAL, "null bound offsets");
+  if (!bounds)  // no byte may be read: every offset is the first, or the list is refused
+    for (uint64_t i = 1; i <= 2ull * nr; ++i)
+      if (bound_off[i] != bound_off[0]) return fail(CB_EINVAL, "null bounds with a non-zero total");
+  if (cb::range_list_first_bad(bounds, bound_off, nr, last_unbounded != 0) >= 0)
+    return fail(CB_EINVAL, "the ranges are not ascending and disjoint (or their offsets decrease)");
+  return CB_OK;
+}
+
+// The tables a scan or a count searches: the non-empty ones, newest first,
+// with their lines' and bytes' totals. *nothing: no device work can find an
+// entry (no lines at all, or lo >= hi in every range).
+struct ScanInput {
+  std::vector<cb::ScanTable> tabs;
+  uint64_t all_lines = 0, all_bytes = 0;
+};
+int scan_input(const cb_table* const* tables, uint32_t nt, const RangeList& rl, uint64_t max_cuts, ScanInput* in,
+               bool* nothing) {
+  if (int rc = for_live_tables(tables, nt, [&](cb_table* ti, uint32_t i) {
+        in->tabs.push_back(cb::ScanTable{ti->data, ti->rec, ti->pfx, ti->fence, ti->llen, ti->nlines, ti->len, i, 0});
+        in->all_lines += ti->nlines;
+        in->all_bytes += ti->len;
+      }))
+    return rc;
+  if (max_cuts && (uint64_t)rl.nr * in->tabs.size() > max_cuts)
+    return fail(CB_EINVAL, "too many cuts (ranges x non-empty tables) for one scan");
+  bool all_empty = true;
+  for (uint32_t i = 0; all_empty && i < rl.nr; ++i) all_empty = rl.empty(i);
+  *nothing = in->tabs.empty() || all_empty;
   return CB_OK;
 }
 
@@ -401,19 +451,13 @@ int scan_copy(const cb_scan* r, uint64_t* off_out, const uint64_t* off, uint8_t*
 // and the kept keys' and values' byte totals at the end, with the ranges'
 // offsets (the result is complete when the call returns); a truncated
 // result's copy is one more.
+// drop_dead (cb_tables_scan_live): the merge's select keeps no tombstone, so
+// every count, rank and offset below is of live entries.
 int scan_ranges(const cb_table* const* tables, uint32_t nt, int dev, const RangeList& rl, uint64_t max_cuts,
-                uint64_t limit, hipStream_t s, void** out) {
-  // the non-empty tables, newest first
-  std::vector<cb::ScanTable> tabs;
-  uint64_t all_lines = 0, all_bytes = 0;
-  if (int rc = for_live_tables(tables, nt, [&](cb_table* ti, uint32_t i) {
-        tabs.push_back(cb::ScanTable{ti->data, ti->rec, ti->pfx, ti->fence, ti->llen, ti->nlines, ti->len, i, 0});
-        all_lines += ti->nlines;
-        all_bytes += ti->len;
-      }))
-    return rc;
-  if (max_cuts && (uint64_t)rl.nr * tabs.size() > max_cuts)
-    return fail(CB_EINVAL, "too many cuts (ranges x non-empty tables) for one scan");
+                uint64_t limit, bool drop_dead, hipStream_t s, void** out) {
+  ScanInput in;
+  bool nothing = false;
+  if (int rc = scan_input(tables, nt, rl, max_cuts, &in, &nothing)) return rc;
   std::unique_ptr<cb_scan, int (*)(void*)> r(new cb_scan(), cb_scan_destroy);
   r->device = dev;
   r->range_off.assign(rl.nr + 1ull, 0);
@@ -423,22 +467,20 @@ int scan_ranges(const cb_table* const* tables, uint32_t nt, int dev, const Range
     *out = r.release();
     return CB_OK;
   };
-  bool all_empty = true;
-  for (uint32_t i = 0; all_empty && i < rl.nr; ++i) all_empty = rl.empty(i);
-  if (tabs.empty() || all_empty) return done();
+  if (nothing) return done();
   int rc = cb_init(dev);
   if (rc) return rc;
   DeviceGuard dg(dev);
   (void)workspace(dev, s);  // (registers s: the pool retires blocks behind it)
   TempBlock cuts{dev}, tmp{dev}, vtmp{dev};
   ScanCuts c;
-  if ((rc = cut_tables(tabs, all_lines, all_bytes, rl, cuts, s, &c))) return rc;
+  if ((rc = cut_tables(in.tabs, in.all_lines, in.all_bytes, rl, cuts, s, &c))) return rc;
   if (!c.n) return done();
   // 3: compaction's merge over the cuts
   Merge mg;
   uint64_t h[3];
   if ((rc = merge_alloc(0, c.n, c.kbound, tmp, &mg))) return rc;
-  if ((rc = enqueue_merge(mg, c.dsrc, c.nsrc, s, h))) return rc;
+  if ((rc = enqueue_merge(mg, c.dsrc, c.nsrc, drop_dead, s, h))) return rc;
   const uint64_t cnt = h[0], len = h[1], kbytes = h[2];
   if (len < kbytes + 2 * cnt) return fail(CB_EHIP, "scan: inconsistent totals");
   if (!cnt) return done();
@@ -456,25 +498,66 @@ int scan_ranges(const cb_table* const* tables, uint32_t nt, int dev, const Range
   return done();
 }
 
-}  // namespace
+// Counts per range without a result (cb_tables_count): the scan's cuts and
+// the merge up to its plain select, then k_scan_count over the sorted records
+// in place of everything a scan does from there on: no tile scans, no result
+// block, no emit, no decode. The counters (2 nr words, zeroed by one memset)
+// come back in one copy, the call's only wait after the cuts' totals, and are
+// checked against the lines inside the ranges before they are handed out.
+// entries / live: host, nr words each, either nullable, zeroed by the caller.
+int count_ranges(const cb_table* const* tables, uint32_t nt, int dev, const RangeList& rl, hipStream_t s,
+                 uint64_t* entries, uint64_t* live) {
+  ScanInput in;
+  bool nothing = false;
+  if (int rc = scan_input(tables, nt, rl, kScanMaxCuts, &in, &nothing)) return rc;
+  if (nothing) return CB_OK;
+  int rc = cb_init(dev);
+  if (rc) return rc;
+  DeviceGuard dg(dev);
+  (void)workspace(dev, s);  // (registers s: the pool retires blocks behind it)
+  TempBlock cuts{dev}, tmp{dev}, cnt{dev};
+  ScanCuts c;
+  if ((rc = cut_tables(in.tabs, in.all_lines, in.all_bytes, rl, cuts, s, &c))) return rc;
+  if (!c.n) return CB_OK;
+  Merge mg;
+  if ((rc = merge_alloc(0, c.n, c.kbound, tmp, &mg))) return rc;
+  cb::Carver cc;
+  const size_t words = 2 * (size_t)rl.nr, o_cnt = cc.take(words * 8);
+  if ((rc = cnt.alloc(cc, "device allocation failed for a count's counters"))) return rc;
+  uint64_t* dcnt = (uint64_t*)cnt.at(o_cnt);
+  if ((rc = enqueue_merge_select(mg, c.dsrc, c.nsrc, false, s))) return rc;
+  HIP_TRY(hipMemsetAsync(dcnt, 0, words * 8, s));
+  HIP_TRY(cb::launch_scan_count(mg.order, mg.side, mg.slen, c.dsrc, c.drng, c.nsrc, mg.n, rl.nr, dcnt, s));
+  std::vector<uint64_t> h(words, 0);
+  HIP_TRY(hipMemcpyAsync(h.data(), dcnt, words * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  uint64_t all = 0;
+  bool ok = true;
+  for (uint32_t r = 0; ok && r < rl.nr; ++r) {
+    ok = h[2 * r] <= c.n - all && h[2 * r + 1] <= h[2 * r];
+    all += h[2 * r];
+  }
+  if (!ok) return fail(CB_EHIP, "count: inconsistent counters");
+  for (uint32_t r = 0; r < rl.nr; ++r) {
+    if (entries) entries[r] = h[2 * r];
+    if (live) live[r] = h[2 * r + 1];
+  }
+  return CB_OK;
+}
 
-extern "C" {
+// A filter of no bits: BloomFilter::insert's `% 0` (src/bloom.rs:36).
+int zero_m_error() { return fail(CB_EZEROM, "attempt to calculate the remainder with a divisor of zero"); }
 
-// Newest-wins merge (compact.hpp). Every temporary is carved from pool blocks
-// released stream-ordered on return (error returns included: nothing the
-// enqueued work touches is freed under it). The call waits for its own stream
-// after staging the sources (pageable memory), for the survivors' totals (the
-// output is sized from them), for the directory's map and at the end (the
-// zone bounds are host results).
-int cb_tables_compact(const cb_table* const* tables, uint32_t nt, uint64_t m_bits, void* stream,
-                      cb_table** table_out, cb_filter** bloom_out) {
+// cb_tables_compact and, with drop_dead, cb_tables_compact_live: the same
+// steps over the same merge, whose select alone knows the difference.
+int compact_tables(const cb_table* const* tables, uint32_t nt, uint64_t m_bits, bool drop_dead, void* stream,
+                   cb_table** table_out, cb_filter** bloom_out) {
   if (!table_out) return fail(CB_EINVAL, "null argument");
   *table_out = nullptr;
   if (bloom_out) *bloom_out = nullptr;
   int dev = 0;
   if (int rc = check_table_list(tables, nt, &dev)) return rc;
-  if (bloom_out && m_bits == 0)  // BloomFilter::insert's `% 0` (src/bloom.rs:36)
-    return fail(CB_EZEROM, "attempt to calculate the remainder with a divisor of zero");
+  if (bloom_out && m_bits == 0) return zero_m_error();
   hipStream_t s = (hipStream_t)stream;
   std::vector<cb::CompactSrc> srcs;
   uint64_t n = 0, kbound = 0;
@@ -496,7 +579,7 @@ int cb_tables_compact(const cb_table* const* tables, uint32_t nt, uint64_t m_bit
   if (n) {
     Merge mg;
     KeptKeys k;
-    if ((rc = merge_sources(srcs, n, kbound, tmp, &mg, s, h))) return rc;
+    if ((rc = merge_sources(srcs, n, kbound, drop_dead, tmp, &mg, s, h))) return rc;
     if ((rc = format_survivors(t.get(), mg, h, keys, &k, s))) return rc;
     if (h[0] && f) {
       // 4: BloomFilter::new(m) + insert per kept key (src/sstable.rs:59-63)
@@ -512,6 +595,36 @@ int cb_tables_compact(const cb_table* const* tables, uint32_t nt, uint64_t m_bit
   return CB_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
+// Newest-wins merge (compact.hpp). Every temporary is carved from pool blocks
+// released stream-ordered on return (error returns included: nothing the
+// enqueued work touches is freed under it). The call waits for its own stream
+// after staging the sources (pageable memory), for the survivors' totals (the
+// output is sized from them), for the directory's map and at the end (the
+// zone bounds are host results).
+int cb_tables_compact(const cb_table* const* tables, uint32_t nt, uint64_t m_bits, void* stream,
+                      cb_table** table_out, cb_filter** bloom_out) {
+  return compact_tables(tables, nt, m_bits, false, stream, table_out, bloom_out);
+}
+
+// The same with the live-row select: tombstones shadow and are then dropped
+// (liverow.hpp). With no tombstone in the inputs it enqueues exactly what
+// cb_tables_compact does.
+// Like the other live-row entries it checks its own arguments before it looks
+// at the table list (cb_tables_compact looks at the list first).
+int cb_tables_compact_live(const cb_table* const* tables, uint32_t nt, uint64_t m_bits, void* stream,
+                           cb_table** table_out, cb_filter** bloom_out) {
+  if (table_out && bloom_out && m_bits == 0) {
+    *table_out = nullptr;
+    *bloom_out = nullptr;
+    return zero_m_error();
+  }
+  return compact_tables(tables, nt, m_bits, true, stream, table_out, bloom_out);
+}
+
 int cb_tables_scan(const cb_table* const* tables, uint32_t nt, const uint8_t* lo, uint64_t lo_len, const uint8_t* hi,
                    uint64_t hi_len, int has_hi, uint64_t limit, void* stream, void** out) {
   if (!out) return fail(CB_EINVAL, "null argument");
@@ -523,7 +636,8 @@ int cb_tables_scan(const cb_table* const* tables, uint32_t nt, const uint8_t* lo
   if (lo_len) std::memcpy(bounds.data(), lo, lo_len);
   if (hi_len) std::memcpy(bounds.data() + lo_len, hi, hi_len);
   const uint64_t off[3] = {0, lo_len, lo_len + hi_len};
-  return scan_ranges(tables, nt, dev, RangeList{bounds.data(), off, 1, !has_hi}, 0, limit, (hipStream_t)stream, out);
+  return scan_ranges(tables, nt, dev, RangeList{bounds.data(), off, 1, !has_hi}, 0, limit, false, (hipStream_t)stream,
+                     out);
 }
 
 int cb_tables_scan_many(const cb_table* const* tables, uint32_t nt, const uint8_t* bounds, const uint64_t* bound_off,
@@ -532,15 +646,39 @@ int cb_tables_scan_many(const cb_table* const* tables, uint32_t nt, const uint8_
   *out = nullptr;
   int dev = 0;
   if (int rc = check_table_list(tables, nt, &dev)) return rc;
-  if (!nr) return fail(CB_EINVAL, "no ranges");
-  if (!bound_off) return fail(CB_EINVAL, "null bound offsets");
-  if (!bounds)  // no byte may be read: every offset is the first, or the list is refused
-    for (uint64_t i = 1; i <= 2ull * nr; ++i)
-      if (bound_off[i] != bound_off[0]) return fail(CB_EINVAL, "null bounds with a non-zero total");
-  if (cb::range_list_first_bad(bounds, bound_off, nr, last_unbounded != 0) >= 0)
-    return fail(CB_EINVAL, "the ranges are not ascending and disjoint (or their offsets decrease)");
-  return scan_ranges(tables, nt, dev, RangeList{bounds, bound_off, nr, last_unbounded != 0}, kScanMaxCuts, 0,
+  if (int rc = check_range_list(bounds, bound_off, nr, last_unbounded)) return rc;
+  return scan_ranges(tables, nt, dev, RangeList{bounds, bound_off, nr, last_unbounded != 0}, kScanMaxCuts, 0, false,
                      (hipStream_t)stream, out);
+}
+
+// cb_tables_scan_many with the live-row select; a limit ranks within one
+// range, so it is legal with one range only.
+int cb_tables_scan_live(const cb_table* const* tables, uint32_t nt, const uint8_t* bounds, const uint64_t* bound_off,
+                        uint32_t nr, int last_unbounded, uint64_t limit, void* stream, void** out) {
+  if (!out) return fail(CB_EINVAL, "null argument");
+  *out = nullptr;
+  // (the call's own arguments before the table list, as in every live-row entry)
+  if (int rc = check_range_list(bounds, bound_off, nr, last_unbounded)) return rc;
+  if (limit && nr != 1) return fail(CB_EINVAL, "a limit takes exactly one range");
+  int dev = 0;
+  if (int rc = check_table_list(tables, nt, &dev)) return rc;
+  return scan_ranges(tables, nt, dev, RangeList{bounds, bound_off, nr, last_unbounded != 0}, kScanMaxCuts, limit, true,
+                     (hipStream_t)stream, out);
+}
+
+int cb_tables_count(const cb_table* const* tables, uint32_t nt, const uint8_t* bounds, const uint64_t* bound_off,
+                    uint32_t nr, int last_unbounded, void* stream, uint64_t* entries, uint64_t* live) {
+  if (!entries && !live) return fail(CB_EINVAL, "null argument");
+  if (entries) std::fill(entries, entries + nr, 0);
+  if (live) std::fill(live, live + nr, 0);
+  // no range: nothing to count (a scan refuses that: its result has a range)
+  if (nr)
+    if (int rc = check_range_list(bounds, bound_off, nr, last_unbounded)) return rc;
+  int dev = 0;
+  if (int rc = check_table_list(tables, nt, &dev)) return rc;
+  if (!nr) return CB_OK;
+  return count_ranges(tables, nt, dev, RangeList{bounds, bound_off, nr, last_unbounded != 0}, (hipStream_t)stream,
+                      entries, live);
 }
 
 int cb_tables_scan_prefixes(const cb_table* const* tables, uint32_t nt, const uint8_t* prefixes,
@@ -561,7 +699,7 @@ int cb_tables_scan_prefixes(const cb_table* const* tables, uint32_t nt, const ui
     return fail(CB_EINVAL, "a prefix without an end before the last one (or prefix offsets that decrease)");
   if (cb::range_list_first_bad(bounds.data(), off.data(), np, last_unbounded) >= 0)
     return fail(CB_EINVAL, "the prefixes are not ascending and disjoint");
-  return scan_ranges(tables, nt, dev, RangeList{bounds.data(), off.data(), np, last_unbounded}, kScanMaxCuts, 0,
+  return scan_ranges(tables, nt, dev, RangeList{bounds.data(), off.data(), np, last_unbounded}, kScanMaxCuts, 0, false,
                      (hipStream_t)stream, out);
 }
 

@@ -12,7 +12,10 @@
 //       record of its run does: one compare with the predecessor in the
 //       common case; only a run with spoiled values walks further back. The
 //       walk reads global memory only, so a run may cross wave, block and
-//       tile edges freely. Each block leaves three tile sums.
+//       tile edges freely. Each block leaves three tile sums. Its DropDead
+//       variant (the live-row entries) also drops a survivor whose own value
+//       is a tombstone (liverow.hpp); the walk is the same, so a tombstone
+//       still defeats the older lines of its key before it is dropped.
 //   k_compact_format — one block per tile: the survivors' offsets from the
 //       scanned tile sums and a block scan, then the block copies the tile's
 //       bytes together, aligned dwords of the output assembled from the
@@ -27,6 +30,7 @@
 #include "blockscan.hpp"
 #include "compact.hpp"
 #include "launch.hpp"
+#include "liverow.hpp"
 #include "profile.hpp"
 #include "zone.hpp"
 
@@ -76,6 +80,7 @@ __device__ __forceinline__ bool same_key(const SortKey& a, const SortKey& b, con
   return bytes_cmp(kb + ko[a.idx] + 16, a.len - 16, kb + ko[b.idx] + 16, b.len - 16) == 0;
 }
 
+template <bool DropDead>
 __global__ __launch_bounds__(kNT) void k_compact_select(const SortKey* __restrict__ order,
                                                         const CompactSide* __restrict__ side,
                                                         const uint8_t* __restrict__ kb,
@@ -88,9 +93,10 @@ __global__ __launch_bounds__(kNT) void k_compact_select(const SortKey* __restric
   if (p < n) {
     const SortKey a = order[p];
     const CompactSide sa = side[a.idx];
-    if (sa.vdl != kBadValue) {
+    // (DropDead is a compile-time constant: the plain kernel has no such test)
+    if (sa.vdl != kBadValue && !(DropDead && value_dead(sa.vdl))) {
       bool keep = true;
-      for (uint64_t q = p; q-- > 0;) {  // the newer lines of the same key
+      for (uint64_t q = p; q-- > 0;) {  // the newer lines of the same key, dead or not
         const SortKey b = order[q];
         if (!same_key(a, b, kb, ko)) break;
         if (side[b.idx].vdl != kBadValue) {
@@ -201,12 +207,12 @@ hipError_t launch_compact_gather(const CompactSrc* src, uint32_t nsrc, uint64_t 
 }
 
 hipError_t launch_compact_select(const SortKey* order, const CompactSide* side, const uint8_t* kb, const uint64_t* ko,
-                                 uint64_t n, uint64_t* slen, uint64_t* tcnt, uint64_t* tbytes, uint64_t* tkeys,
-                                 hipStream_t s) {
+                                 uint64_t n, bool drop_dead, uint64_t* slen, uint64_t* tcnt, uint64_t* tbytes,
+                                 uint64_t* tkeys, hipStream_t s) {
   if (!n) return hipSuccess;
-  ProfScope ps("k_compact_select", s);
-  hipLaunchKernelGGL(k_compact_select, dim3(blocks_for(n, kNT)), dim3(kNT), 0, s, order, side, kb, ko, n, slen, tcnt,
-                     tbytes, tkeys);
+  ProfScope ps(drop_dead ? "k_compact_select_live" : "k_compact_select", s);
+  const auto k = drop_dead ? k_compact_select<true> : k_compact_select<false>;
+  hipLaunchKernelGGL(k, dim3(blocks_for(n, kNT)), dim3(kNT), 0, s, order, side, kb, ko, n, slen, tcnt, tbytes, tkeys);
   return hipGetLastError();
 }
 

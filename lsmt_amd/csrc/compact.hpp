@@ -69,10 +69,14 @@ hipError_t launch_compact_gather(const CompactSrc* src, uint32_t nsrc, uint64_t 
 // Over the sorted records (equal keys adjacent, newest first): slen[p] = the
 // output line's length (with its '\n') when record p is its key's newest line
 // with a decodable value, else 0; per tile of kCompactTile records the number
-// of survivors, their line bytes and their key bytes.
+// of survivors, their line bytes and their key bytes. drop_dead (the live-row
+// entries; a compile-time variant of the kernel): such a record survives only
+// when its own value is not a tombstone (liverow.hpp) either. A tombstone
+// shadows and is then dropped: it still defeats every older line of its key,
+// so no older value comes back for a deleted row.
 hipError_t launch_compact_select(const SortKey* order, const CompactSide* side, const uint8_t* kb, const uint64_t* ko,
-                                 uint64_t n, uint64_t* slen, uint64_t* tcnt, uint64_t* tbytes, uint64_t* tkeys,
-                                 hipStream_t s);
+                                 uint64_t n, bool drop_dead, uint64_t* slen, uint64_t* tcnt, uint64_t* tbytes,
+                                 uint64_t* tkeys, hipStream_t s);
 // From the scanned tile sums: the file (out: the survivors' lines `key \t
 // text \n` back to back), its line index without re-reading it (sstable.hpp
 // layout: survivor l is line l of nl; vdl carried over from the input's

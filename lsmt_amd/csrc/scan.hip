@@ -23,10 +23,15 @@
 //       it also writes each survivor's range.
 //   k_scan_range_off — one lane per range: where its entries begin, the lower
 //       bound of its number in the survivors' ranges (they ascend with the keys).
+//   k_scan_count — cb_tables_count's tail, in place of the emit and all after
+//       it: one block per tile of sorted records, the survivors and the live
+//       ones (liverow.hpp) summed per run of equal ranges and added to the
+//       ranges' counters. No key is copied and no value read.
 #include <hip/hip_runtime.h>
 
 #include "blockscan.hpp"
 #include "launch.hpp"
+#include "liverow.hpp"
 #include "profile.hpp"
 #include "scan.hpp"
 #include "tablesearch.hpp"
@@ -258,6 +263,51 @@ __global__ __launch_bounds__(kNT) void k_scan_range_off(const uint32_t* __restri
   range_off[r] = lo;
 }
 
+// One block per tile of sorted records, after the plain select. Every record,
+// survivor or not, has its source's range, and the ranges do not decrease
+// along the sorted order, so a tile is a few runs of equal ranges. One block
+// scan of two packed flags (survivor in the low word, survivor and not dead
+// in the high one: neither passes 256), then each lane that ends a run adds
+// the run's two sums to its range's counters: as many pairs of atomics as the
+// tile holds ranges with an entry.
+__global__ __launch_bounds__(kNT) void k_scan_count(const SortKey* __restrict__ order,
+                                                    const CompactSide* __restrict__ side,
+                                                    const uint64_t* __restrict__ slen,
+                                                    const CompactSrc* __restrict__ src,
+                                                    const uint32_t* __restrict__ src_rng, uint32_t nsrc, uint64_t n,
+                                                    uint32_t nr, uint64_t* __restrict__ cnt) {
+  constexpr uint32_t kPast = 0xFFFFFFFFu;  // the range of a lane past the last record (nr - 1 is below it)
+  __shared__ uint32_t s_rid[kNT + 1];
+  __shared__ uint64_t s_inc[kNT];  // the inclusive scan of the packed flags
+  const uint32_t t = threadIdx.x;
+  const uint64_t p = (uint64_t)blockIdx.x * kNT + t;
+  uint32_t rid = kPast;
+  uint64_t v = 0;
+  if (p < n) {
+    const uint32_t g = order[p].idx;
+    rid = nr > 1 ? src_rng[src_of(src, nsrc, g)] : 0;  // (uniform)
+    if (slen[p]) v = value_dead(side[g].vdl) ? 1ull : 1ull | 1ull << 32;
+  }
+  uint64_t total;
+  const uint64_t inc = block_scan<(int)kNT>(v, &total) + v;
+  s_rid[t] = rid;
+  s_inc[t] = inc;
+  if (t == 0) s_rid[kNT] = kPast;
+  __syncthreads();
+  if (p >= n || s_rid[t + 1] == rid || rid >= nr) return;  // not the end of a run
+  // the run's first lane: the first of the tile with this range
+  uint32_t lo = 0, hi = t;  // s_rid[i] < rid for i < lo, s_rid[hi] == rid
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (s_rid[mid] < rid) lo = mid + 1;
+    else hi = mid;
+  }
+  const uint64_t sum = inc - (lo ? s_inc[lo - 1] : 0);
+  const unsigned long long entries = sum & 0xFFFFFFFFull, live = sum >> 32;
+  if (entries) atomicAdd((unsigned long long*)(cnt + 2ull * rid), entries);
+  if (live) atomicAdd((unsigned long long*)(cnt + 2ull * rid + 1), live);
+}
+
 }  // namespace
 
 hipError_t launch_scan_bounds(const ScanTable* tab, uint32_t nt, const ScanRange* rng, uint32_t nr,
@@ -285,6 +335,16 @@ hipError_t launch_scan_emit(const SortKey* order, const CompactSide* side, const
   ProfScope ps("k_scan_emit", s);
   hipLaunchKernelGGL(k_scan_emit, dim3(blocks_for(n, kNT)), dim3(kNT), 0, s, order, side, slen, tcnt, tkeys, totals,
                      src, src_tab, src_rng, nsrc, n, count, keys, key_off, which, rid, vsrc, dlen, vsum);
+  return hipGetLastError();
+}
+
+hipError_t launch_scan_count(const SortKey* order, const CompactSide* side, const uint64_t* slen,
+                             const CompactSrc* src, const uint32_t* src_rng, uint32_t nsrc, uint64_t n, uint32_t nr,
+                             uint64_t* cnt, hipStream_t s) {
+  if (!n || !nr) return hipSuccess;
+  ProfScope ps("k_scan_count", s);
+  hipLaunchKernelGGL(k_scan_count, dim3(blocks_for(n, kNT)), dim3(kNT), 0, s, order, side, slen, src, src_rng, nsrc,
+                     n, nr, cnt);
   return hipGetLastError();
 }
 

@@ -87,5 +87,13 @@ hipError_t launch_scan_emit(const SortKey* order, const CompactSide* side, const
 // lower bound of r in the non-decreasing rid[0..count)), so range r's entries
 // are [range_off[r], range_off[r + 1]), range_off[0] = 0, range_off[nr] = count.
 hipError_t launch_scan_range_off(const uint32_t* rid, uint64_t count, uint32_t nr, uint64_t* range_off, hipStream_t s);
+// Counts without a result (cb_tables_count), over the sorted records and the
+// plain launch_compact_select's slen: cnt[2 r] += the survivors whose source
+// lies in range r (the entries a scan of r returns), cnt[2 r + 1] += those of
+// them whose value is not dead (liverow.hpp). The caller zeroes cnt (2 nr
+// words). src_rng as launch_scan_sources left it (not read when nr == 1).
+hipError_t launch_scan_count(const SortKey* order, const CompactSide* side, const uint64_t* slen,
+                             const CompactSrc* src, const uint32_t* src_rng, uint32_t nsrc, uint64_t n, uint32_t nr,
+                             uint64_t* cnt, hipStream_t s);
 
 }  // namespace cb
