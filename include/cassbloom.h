@@ -503,6 +503,65 @@ int cb_scan_which(const void* r, int32_t* which /* count */);
 /* Retires the result's memory through the block pool, like every other
  * handle: no device-wide synchronise. */
 int cb_scan_destroy(void* r);
+/* ---- last-write-wins by row timestamp: tables as replicas --------------------
+ * Every row the reference writes is stamped by its coordinator and stored as
+ * 8 bytes of big-endian timestamp, then the payload (insert_ns_ts,
+ * src/lib.rs:154-158); split_ts (src/query.rs:21-27) takes it off again:
+ *   ts(value) = 0 when the decoded length is below 8, else the first 8
+ *               decoded bytes as an unsigned big-endian u64.
+ * Writes are forwarded with their timestamp, so a replica's arrival order,
+ * and with it its table order, need not be timestamp order, and the cluster's
+ * read reconciles by timestamp, not by position: it folds the replicas'
+ * `key \t ts \t val` lines (exec_select_schema with meta, src/query.rs:393-410)
+ * with "keep the current row if cur_ts >= ts, else replace"
+ * (src/cluster.rs:405-416), and drops the rows whose val is empty only after
+ * the fold (src/cluster.rs:454-459).
+ * THE RULE. For tables T[0..nt), table r stands for replica r. Its answer for
+ * key k is its line for k if that line's value decodes, else it has none (a
+ * well-formed table has at most one line per key). The WINNER for k is the
+ * answer with the greatest ts and, among equal ts, of the lowest table index;
+ * a key without an answer has no winner and is absent. With drop_dead a
+ * winner whose value is dead (the live-row section's rule: no payload) is
+ * then absent too. It still defeated every line with ts <= its own, and a
+ * tombstone that LOSES to a row with a newer ts deletes nothing, whichever
+ * table is newer. That is the difference from the live-row entries above:
+ * cb_tables_compact_live lets a tombstone in a newer table delete a row of an
+ * older table even when the row's timestamp is the newer one; the entries
+ * here do not. With timestamps that strictly descend in table order for every
+ * key both rules choose the same lines.
+ * THE CALLER'S RULE for drop_dead is cb_tables_compact_live's: dropping
+ * winners is correct only when no table or replica of the store stays outside
+ * the list; a tombstone that is dropped can no longer defeat an older row
+ * held elsewhere. The library cannot check this.
+ * The newest-wins entries above are unchanged. All three entries below check
+ * their own arguments (outputs, range list, limit, m_bits) before they look
+ * at the table list, and clear their outputs on every refusal. */
+/* cb_tables_compact's contract with "newest decodable line" replaced by the
+ * winner: the file is SsTable::create of { (k, winner(k)) }, with its line
+ * index, Bloom filter and zone bounds; no winner at all gives the empty file.
+ * Arguments, errors and waits as cb_tables_compact. Next to it the call reads
+ * about 11 bytes and writes 8 per input line (the timestamps) and enqueues
+ * two more launches. */
+int cb_tables_compact_lww(const cb_table* const* tables, uint32_t nt, uint64_t m_bits, int drop_dead,
+                          void* stream, cb_table** table_out, cb_filter** bloom_out /* nullable */);
+/* cb_tables_scan_live's call over the winners: range lists, the cut cap, the
+ * refusals, "limit > 0 only with nr == 1" (`truncated` says whether more
+ * winners qualified), the cb_scan_* accessors and cb_scan_ranges are the
+ * same. which[i] = the winner's index in tables[]; cb_scan_ts gives its ts. */
+int cb_tables_scan_lww(const cb_table* const* tables, uint32_t nt, const uint8_t* bounds,
+                       const uint64_t* bound_off, uint32_t nr, int last_unbounded, int drop_dead,
+                       uint64_t limit, void* stream, void** out /* cb_scan */);
+/* cb_tables_count's contract over the winners: entries[r] = the winners in
+ * range r (cb_tables_scan_lww's entries with drop_dead 0), live[r] = those of
+ * them that are not dead (its entries with drop_dead 1). */
+int cb_tables_count_lww(const cb_table* const* tables, uint32_t nt, const uint8_t* bounds,
+                        const uint64_t* bound_off, uint32_t nr, int last_unbounded, void* stream,
+                        uint64_t* entries /* winners */, uint64_t* live /* winners that are not dead */);
+/* ts[i] = ts(value i) of a result of any cb_tables_scan* call: 0 for a value
+ * below 8 bytes. ts: count uint64, host or device memory, as cb_scan_which
+ * copies. Nothing is written for an empty result; a NULL ts returns CB_OK.
+ * Synchronous. */
+int cb_scan_ts(const void* r, uint64_t* ts /* count; host or device, as cb_scan_which */);
 /* Finalise a table from cb_sstable_create*: wait for its work, take its
  * results; returns its deferred error, if any. Idempotent, thread-safe. */
 int cb_table_wait(const cb_table* t);

@@ -922,6 +922,17 @@ class ScanResult:
         self.copy_which(w)
         return w[:self.count]
 
+    def copy_ts(self, ts) -> None:
+        check(_L().cb_scan_ts(self._h, _ptr_of(ts)[0]))
+
+    def ts(self) -> np.ndarray:
+        """uint64[count]: every entry's write timestamp, the first 8 bytes of
+        its value as a big-endian integer, 0 for a value below 8 bytes
+        (cb_scan_ts; the reference's split_ts, src/query.rs:21-27)."""
+        t = np.zeros(max(self.count, 1), np.uint64)
+        self.copy_ts(t)
+        return t[:self.count]
+
     def items(self) -> "list[tuple[bytes, bytes]]":
         return list(zip(self.keys(), self.values()))
 
@@ -1080,6 +1091,58 @@ def compact_live(tables: Sequence[Table], m: int = 1024, stream=None):
     if table.nlines:
         zone = ZoneMap(table._zone(0), table._zone(1))
     return table, bloom, zone
+
+
+def compact_lww(tables: Sequence[Table], m: int = 1024, drop_dead: bool = False, stream=None):
+    """compact() with last-write-wins by row timestamp in place of newest-wins
+    (cb_tables_compact_lww): table r stands for replica r, and a key keeps its
+    decodable line with the greatest timestamp (the first 8 value bytes,
+    big-endian; 0 below 8 bytes), the lowest table index among equal
+    timestamps: the fold the reference's coordinator runs over its replicas'
+    rows (src/cluster.rs:405-416). Use it where table order is not write
+    order: tables of several replicas (repair, bootstrap), or forwarded writes
+    that arrived out of order. A tombstone that loses to a row with a newer
+    timestamp deletes nothing, whichever table is newer (compact_live would
+    drop that row). drop_dead: winners that are tombstones are then left out
+    (src/cluster.rs:454-459); correct only when no table or replica of the
+    store stays outside `tables`. Returns (Table, BloomFilter, ZoneMap) as
+    compact does."""
+    arr, dev = _table_list(tables)
+    th, fh = ctypes.c_void_p(), ctypes.c_void_p()
+    _raise(_L().cb_tables_compact_lww(arr, len(tables), int(m), int(bool(drop_dead)), _stream(stream),
+                                      ctypes.byref(th), ctypes.byref(fh)))
+    table = Table._adopt(th.value, dev)
+    bloom = BloomFilter(0, device=dev, _handle=fh.value)
+    zone = ZoneMap()
+    if table.nlines:
+        zone = ZoneMap(table._zone(0), table._zone(1))
+    return table, bloom, zone
+
+
+def scan_lww(tables: Sequence[Table], ranges=None, prefixes=None, limit: int = 0, drop_dead: bool = False,
+             stream=None) -> ScanResult:
+    """scan_many under compact_lww's rule (cb_tables_scan_lww): every key's
+    entry is its winner by timestamp, which() its table's index in `tables`
+    and ts() its timestamp. drop_dead leaves out the winners that are
+    tombstones. limit > 0 takes exactly one range, as in scan_live."""
+    data, off, nr, last_unbounded = _range_list(ranges, prefixes)
+    arr, dev = _table_list(tables)
+    h = ctypes.c_void_p()
+    _raise(_L().cb_tables_scan_lww(arr, len(tables), data, _ptr_of(off)[0], nr, last_unbounded, int(bool(drop_dead)),
+                                   int(limit), _stream(stream), ctypes.byref(h)))
+    return ScanResult(h.value, dev)
+
+
+def count_lww(tables: Sequence[Table], ranges=None, prefixes=None, stream=None):
+    """count() under compact_lww's rule (cb_tables_count_lww): (entries, live),
+    per range the winners and the winners that are not tombstones, i.e. the
+    sizes of scan_lww's ranges with drop_dead False and True."""
+    data, off, nr, last_unbounded = _range_list(ranges, prefixes)
+    arr, _ = _table_list(tables)
+    entries, live = np.zeros(max(nr, 1), np.uint64), np.zeros(max(nr, 1), np.uint64)
+    _raise(_L().cb_tables_count_lww(arr, len(tables), data, _ptr_of(off)[0], nr, last_unbounded, _stream(stream),
+                                    _ptr_of(entries)[0], _ptr_of(live)[0]))
+    return entries[:nr], live[:nr]
 
 
 def _to_var(b: KeyBatch) -> KeyBatch:

@@ -5,18 +5,28 @@
 // the result's accessors (cb_scan_*). The live-row entries run the same steps:
 // cb_tables_compact_live and cb_tables_scan_live with the select that drops
 // tombstones (liverow.hpp), cb_tables_count with the plain select and a
-// counting kernel in place of the scan's tail.
+// counting kernel in place of the scan's tail. The LWW entries
+// (cb_tables_compact_lww, cb_tables_scan_lww, cb_tables_count_lww) run them
+// with the select that keeps a key's line of the greatest timestamp
+// (rowts.hpp) in place of its newest one; cb_scan_ts reads the timestamps of
+// any result.
 //
 // Reference: src/sstable.rs:51-98 (the file a compaction writes),
-// src/lib.rs:125-146 (Database::get, whose answers both reproduce).
+// src/lib.rs:125-146 (Database::get, whose answers both reproduce), src/cluster.rs:405-416,
+// 454-459 (the read's fold by timestamp, which the LWW entries reproduce).
 #include "capi_table.hpp"
 #include "compact.hpp"
 #include "keyrange.hpp"
 #include "scan.hpp"
 
 using namespace cbx;
+using cb::MergeOrder;
+using cb::MergeRule;
 
 namespace {
+
+constexpr MergeRule kNewest{MergeOrder::newest, false};  // the plain entries' rule
+constexpr MergeRule kLive{MergeOrder::newest, true};     // the live-row entries'
 
 // ---- the table list both entries take ----
 
@@ -61,9 +71,10 @@ struct Merge {
   cb::SortKey* order = nullptr;
   uint8_t* sort = nullptr;
   uint64_t *slen = nullptr, *tcnt = nullptr, *tbytes = nullptr, *tkeys = nullptr, *tot = nullptr;
+  uint64_t* ts = nullptr;  // the lines' timestamps: an LWW merge's only
   cb::CreateResult* dr = nullptr;
 };
-int merge_alloc(uint32_t nsrc_cap, uint64_t n, uint64_t kbound, TempBlock& tmp, Merge* m) {
+int merge_alloc(uint32_t nsrc_cap, uint64_t n, uint64_t kbound, MergeOrder order, TempBlock& tmp, Merge* m) {
   m->n = n;
   m->kbound = kbound;
   m->tiles = cb::compact_tiles(n);
@@ -74,7 +85,7 @@ int merge_alloc(uint32_t nsrc_cap, uint64_t n, uint64_t kbound, TempBlock& tmp, 
                o_side = c.take(n * sizeof(cb::CompactSide)), o_order = c.take(n * sizeof(cb::SortKey)),
                o_sort = c.take(m->plan.tmp_bytes), o_slen = c.take(n * 8), o_tcnt = c.take(m->tiles * 8),
                o_tbytes = c.take(m->tiles * 8), o_tkeys = c.take(m->tiles * 8), o_tot = c.take(3 * 8),
-               o_res = c.take(sizeof(cb::CreateResult));
+               o_res = c.take(sizeof(cb::CreateResult)), o_ts = c.take(order == MergeOrder::lww ? n * 8 : 0);
   if (int rc = tmp.alloc(c, "device allocation failed for a merge's scratch")) return rc;
   m->dsrc = (cb::CompactSrc*)tmp.at(o_src);
   m->klen = (uint64_t*)tmp.at(o_klen);
@@ -90,13 +101,16 @@ int merge_alloc(uint32_t nsrc_cap, uint64_t n, uint64_t kbound, TempBlock& tmp, 
   m->tkeys = (uint64_t*)tmp.at(o_tkeys);
   m->tot = (uint64_t*)tmp.at(o_tot);
   m->dr = (cb::CreateResult*)tmp.at(o_res);
+  m->ts = order == MergeOrder::lww ? (uint64_t*)tmp.at(o_ts) : nullptr;
   return CB_OK;
 }
 // The merge of sources dsrc[0..nsrc) (device, m.n lines in all) on s, up to
 // and including the select (nothing is waited for): the sorted order and, per
-// sorted record, whether it survives (slen) with the tiles' sums. drop_dead:
-// the live-row entries' select, which keeps no tombstone (liverow.hpp).
-int enqueue_merge_select(const Merge& m, const cb::CompactSrc* dsrc, uint32_t nsrc, bool drop_dead, hipStream_t s) {
+// sorted record, whether it survives (slen) with the tiles' sums. The rule
+// (compact.hpp) picks the select: newest enqueues k_compact_select, lww the
+// lines' timestamps and the two launches of the LWW select (m was allocated
+// for the same order); drop_dead: either keeps no tombstone (liverow.hpp).
+int enqueue_merge_select(const Merge& m, const cb::CompactSrc* dsrc, uint32_t nsrc, MergeRule rule, hipStream_t s) {
   const uint64_t n = m.n;
   HIP_TRY(cb::launch_compact_klen(dsrc, nsrc, n, m.klen, s));
   HIP_TRY(cb::launch_scan_u64(m.klen, m.ko, n, m.scan, s));
@@ -107,7 +121,15 @@ int enqueue_merge_select(const Merge& m, const cb::CompactSrc* dsrc, uint32_t ns
   // the stable sort by key, input index last: a key's lines leave it
   // adjacent, newest first
   if (int rc = enqueue_key_sort(m.plan, m.kb, m.ko, n, m.order, m.sort, m.dr, s, nullptr, nullptr, nullptr)) return rc;
-  HIP_TRY(cb::launch_compact_select(m.order, m.side, m.kb, m.ko, n, drop_dead, m.slen, m.tcnt, m.tbytes, m.tkeys, s));
+  if (rule.order == MergeOrder::newest) {
+    HIP_TRY(cb::launch_compact_select(m.order, m.side, m.kb, m.ko, n, rule.drop_dead, m.slen, m.tcnt, m.tbytes,
+                                      m.tkeys, s));
+    return CB_OK;
+  }
+  // (the sort moves records, not lines: ts is indexed like side, by input line)
+  HIP_TRY(cb::launch_compact_ts(m.side, n, m.ts, s));
+  HIP_TRY(cb::launch_compact_select_lww(m.order, m.side, m.ts, m.kb, m.ko, n, rule.drop_dead, m.slen, m.tcnt,
+                                        m.tbytes, m.tkeys, s));
   return CB_OK;
 }
 // The rest of the merge for a caller that writes the survivors out: the scans
@@ -115,10 +137,10 @@ int enqueue_merge_select(const Merge& m, const cb::CompactSrc* dsrc, uint32_t ns
 // bytes}, read back (they size the caller's output), the stream waited for,
 // and checked against the inputs' bounds before anything is sized from them.
 // (A count stops at the select: it places no survivor.)
-int enqueue_merge(const Merge& m, const cb::CompactSrc* dsrc, uint32_t nsrc, bool drop_dead, hipStream_t s,
+int enqueue_merge(const Merge& m, const cb::CompactSrc* dsrc, uint32_t nsrc, MergeRule rule, hipStream_t s,
                   uint64_t (&h)[3]) {
   const uint64_t n = m.n;
-  if (int rc = enqueue_merge_select(m, dsrc, nsrc, drop_dead, s)) return rc;
+  if (int rc = enqueue_merge_select(m, dsrc, nsrc, rule, s)) return rc;
   HIP_TRY(cb::launch_tile_scan(m.tcnt, m.tiles, m.tot + 0, s));
   HIP_TRY(cb::launch_tile_scan(m.tbytes, m.tiles, m.tot + 1, s));
   HIP_TRY(cb::launch_tile_scan(m.tkeys, m.tiles, m.tot + 2, s));
@@ -153,13 +175,13 @@ int compact_sources(const cb_table* const* tables, uint32_t nt, std::vector<cb::
 
 // 2: the merge over the sources, staged into its scratch (one wait: the
 // source is pageable), up to the survivors' totals h (enqueue_merge's wait).
-int merge_sources(const std::vector<cb::CompactSrc>& srcs, uint64_t n, uint64_t kbound, bool drop_dead,
+int merge_sources(const std::vector<cb::CompactSrc>& srcs, uint64_t n, uint64_t kbound, MergeRule rule,
                   TempBlock& tmp, Merge* mg, hipStream_t s, uint64_t (&h)[3]) {
   const uint32_t nsrc = (uint32_t)srcs.size();
-  if (int rc = merge_alloc(nsrc, n, kbound, tmp, mg)) return rc;
+  if (int rc = merge_alloc(nsrc, n, kbound, rule.order, tmp, mg)) return rc;
   HIP_TRY(hipMemcpyAsync(mg->dsrc, srcs.data(), nsrc * sizeof(cb::CompactSrc), hipMemcpyHostToDevice, s));
   HIP_TRY(hipStreamSynchronize(s));  // the source is pageable
-  return enqueue_merge(*mg, mg->dsrc, nsrc, drop_dead, s, h);
+  return enqueue_merge(*mg, mg->dsrc, nsrc, rule, s, h);
 }
 
 // 3: the survivors (h = {lines, file bytes, key bytes}) formatted into t: the
@@ -451,10 +473,12 @@ int scan_copy(const cb_scan* r, uint64_t* off_out, const uint64_t* off, uint8_t*
 // and the kept keys' and values' byte totals at the end, with the ranges'
 // offsets (the result is complete when the call returns); a truncated
 // result's copy is one more.
-// drop_dead (cb_tables_scan_live): the merge's select keeps no tombstone, so
-// every count, rank and offset below is of live entries.
+// rule: the merge's select (compact.hpp). With drop_dead (cb_tables_scan_live)
+// it keeps no tombstone, so every count, rank and offset below is of live
+// entries; with the lww order (cb_tables_scan_lww) an entry is its key's line
+// of the greatest timestamp, and `which` that line's table.
 int scan_ranges(const cb_table* const* tables, uint32_t nt, int dev, const RangeList& rl, uint64_t max_cuts,
-                uint64_t limit, bool drop_dead, hipStream_t s, void** out) {
+                uint64_t limit, MergeRule rule, hipStream_t s, void** out) {
   ScanInput in;
   bool nothing = false;
   if (int rc = scan_input(tables, nt, rl, max_cuts, &in, &nothing)) return rc;
@@ -479,8 +503,8 @@ int scan_ranges(const cb_table* const* tables, uint32_t nt, int dev, const Range
   // 3: compaction's merge over the cuts
   Merge mg;
   uint64_t h[3];
-  if ((rc = merge_alloc(0, c.n, c.kbound, tmp, &mg))) return rc;
-  if ((rc = enqueue_merge(mg, c.dsrc, c.nsrc, drop_dead, s, h))) return rc;
+  if ((rc = merge_alloc(0, c.n, c.kbound, rule.order, tmp, &mg))) return rc;
+  if ((rc = enqueue_merge(mg, c.dsrc, c.nsrc, rule, s, h))) return rc;
   const uint64_t cnt = h[0], len = h[1], kbytes = h[2];
   if (len < kbytes + 2 * cnt) return fail(CB_EHIP, "scan: inconsistent totals");
   if (!cnt) return done();
@@ -505,8 +529,10 @@ int scan_ranges(const cb_table* const* tables, uint32_t nt, int dev, const Range
 // come back in one copy, the call's only wait after the cuts' totals, and are
 // checked against the lines inside the ranges before they are handed out.
 // entries / live: host, nr words each, either nullable, zeroed by the caller.
-int count_ranges(const cb_table* const* tables, uint32_t nt, int dev, const RangeList& rl, hipStream_t s,
-                 uint64_t* entries, uint64_t* live) {
+// order: which line of a key is its entry (cb_tables_count_lww: the winner by
+// timestamp); no order drops anything here, live is counted beside entries.
+int count_ranges(const cb_table* const* tables, uint32_t nt, int dev, const RangeList& rl, MergeOrder order,
+                 hipStream_t s, uint64_t* entries, uint64_t* live) {
   ScanInput in;
   bool nothing = false;
   if (int rc = scan_input(tables, nt, rl, kScanMaxCuts, &in, &nothing)) return rc;
@@ -520,12 +546,12 @@ int count_ranges(const cb_table* const* tables, uint32_t nt, int dev, const Rang
   if ((rc = cut_tables(in.tabs, in.all_lines, in.all_bytes, rl, cuts, s, &c))) return rc;
   if (!c.n) return CB_OK;
   Merge mg;
-  if ((rc = merge_alloc(0, c.n, c.kbound, tmp, &mg))) return rc;
+  if ((rc = merge_alloc(0, c.n, c.kbound, order, tmp, &mg))) return rc;
   cb::Carver cc;
   const size_t words = 2 * (size_t)rl.nr, o_cnt = cc.take(words * 8);
   if ((rc = cnt.alloc(cc, "device allocation failed for a count's counters"))) return rc;
   uint64_t* dcnt = (uint64_t*)cnt.at(o_cnt);
-  if ((rc = enqueue_merge_select(mg, c.dsrc, c.nsrc, false, s))) return rc;
+  if ((rc = enqueue_merge_select(mg, c.dsrc, c.nsrc, MergeRule{order, false}, s))) return rc;
   HIP_TRY(hipMemsetAsync(dcnt, 0, words * 8, s));
   HIP_TRY(cb::launch_scan_count(mg.order, mg.side, mg.slen, c.dsrc, c.drng, c.nsrc, mg.n, rl.nr, dcnt, s));
   std::vector<uint64_t> h(words, 0);
@@ -548,9 +574,10 @@ int count_ranges(const cb_table* const* tables, uint32_t nt, int dev, const Rang
 // A filter of no bits: BloomFilter::insert's `% 0` (src/bloom.rs:36).
 int zero_m_error() { return fail(CB_EZEROM, "attempt to calculate the remainder with a divisor of zero"); }
 
-// cb_tables_compact and, with drop_dead, cb_tables_compact_live: the same
-// steps over the same merge, whose select alone knows the difference.
-int compact_tables(const cb_table* const* tables, uint32_t nt, uint64_t m_bits, bool drop_dead, void* stream,
+// cb_tables_compact and, by their rules, cb_tables_compact_live and
+// cb_tables_compact_lww: the same steps over the same merge, whose select
+// alone knows the difference.
+int compact_tables(const cb_table* const* tables, uint32_t nt, uint64_t m_bits, MergeRule rule, void* stream,
                    cb_table** table_out, cb_filter** bloom_out) {
   if (!table_out) return fail(CB_EINVAL, "null argument");
   *table_out = nullptr;
@@ -579,7 +606,7 @@ int compact_tables(const cb_table* const* tables, uint32_t nt, uint64_t m_bits, 
   if (n) {
     Merge mg;
     KeptKeys k;
-    if ((rc = merge_sources(srcs, n, kbound, drop_dead, tmp, &mg, s, h))) return rc;
+    if ((rc = merge_sources(srcs, n, kbound, rule, tmp, &mg, s, h))) return rc;
     if ((rc = format_survivors(t.get(), mg, h, keys, &k, s))) return rc;
     if (h[0] && f) {
       // 4: BloomFilter::new(m) + insert per kept key (src/sstable.rs:59-63)
@@ -607,7 +634,7 @@ extern "C" {
 // zone bounds are host results).
 int cb_tables_compact(const cb_table* const* tables, uint32_t nt, uint64_t m_bits, void* stream,
                       cb_table** table_out, cb_filter** bloom_out) {
-  return compact_tables(tables, nt, m_bits, false, stream, table_out, bloom_out);
+  return compact_tables(tables, nt, m_bits, kNewest, stream, table_out, bloom_out);
 }
 
 // The same with the live-row select: tombstones shadow and are then dropped
@@ -622,7 +649,7 @@ int cb_tables_compact_live(const cb_table* const* tables, uint32_t nt, uint64_t 
     *bloom_out = nullptr;
     return zero_m_error();
   }
-  return compact_tables(tables, nt, m_bits, true, stream, table_out, bloom_out);
+  return compact_tables(tables, nt, m_bits, kLive, stream, table_out, bloom_out);
 }
 
 int cb_tables_scan(const cb_table* const* tables, uint32_t nt, const uint8_t* lo, uint64_t lo_len, const uint8_t* hi,
@@ -636,7 +663,7 @@ int cb_tables_scan(const cb_table* const* tables, uint32_t nt, const uint8_t* lo
   if (lo_len) std::memcpy(bounds.data(), lo, lo_len);
   if (hi_len) std::memcpy(bounds.data() + lo_len, hi, hi_len);
   const uint64_t off[3] = {0, lo_len, lo_len + hi_len};
-  return scan_ranges(tables, nt, dev, RangeList{bounds.data(), off, 1, !has_hi}, 0, limit, false, (hipStream_t)stream,
+  return scan_ranges(tables, nt, dev, RangeList{bounds.data(), off, 1, !has_hi}, 0, limit, kNewest, (hipStream_t)stream,
                      out);
 }
 
@@ -647,7 +674,7 @@ int cb_tables_scan_many(const cb_table* const* tables, uint32_t nt, const uint8_
   int dev = 0;
   if (int rc = check_table_list(tables, nt, &dev)) return rc;
   if (int rc = check_range_list(bounds, bound_off, nr, last_unbounded)) return rc;
-  return scan_ranges(tables, nt, dev, RangeList{bounds, bound_off, nr, last_unbounded != 0}, kScanMaxCuts, 0, false,
+  return scan_ranges(tables, nt, dev, RangeList{bounds, bound_off, nr, last_unbounded != 0}, kScanMaxCuts, 0, kNewest,
                      (hipStream_t)stream, out);
 }
 
@@ -662,7 +689,7 @@ int cb_tables_scan_live(const cb_table* const* tables, uint32_t nt, const uint8_
   if (limit && nr != 1) return fail(CB_EINVAL, "a limit takes exactly one range");
   int dev = 0;
   if (int rc = check_table_list(tables, nt, &dev)) return rc;
-  return scan_ranges(tables, nt, dev, RangeList{bounds, bound_off, nr, last_unbounded != 0}, kScanMaxCuts, limit, true,
+  return scan_ranges(tables, nt, dev, RangeList{bounds, bound_off, nr, last_unbounded != 0}, kScanMaxCuts, limit, kLive,
                      (hipStream_t)stream, out);
 }
 
@@ -677,8 +704,47 @@ int cb_tables_count(const cb_table* const* tables, uint32_t nt, const uint8_t* b
   int dev = 0;
   if (int rc = check_table_list(tables, nt, &dev)) return rc;
   if (!nr) return CB_OK;
-  return count_ranges(tables, nt, dev, RangeList{bounds, bound_off, nr, last_unbounded != 0}, (hipStream_t)stream,
-                      entries, live);
+  return count_ranges(tables, nt, dev, RangeList{bounds, bound_off, nr, last_unbounded != 0}, MergeOrder::newest,
+                      (hipStream_t)stream, entries, live);
+}
+
+// The LWW entries: the live-row entries' argument order (their own arguments
+// before the table list, outputs cleared on every refusal) and the same steps
+// under the lww order; drop_dead drops the winners that are tombstones.
+int cb_tables_compact_lww(const cb_table* const* tables, uint32_t nt, uint64_t m_bits, int drop_dead, void* stream,
+                          cb_table** table_out, cb_filter** bloom_out) {
+  if (table_out && bloom_out && m_bits == 0) {
+    *table_out = nullptr;
+    *bloom_out = nullptr;
+    return zero_m_error();
+  }
+  return compact_tables(tables, nt, m_bits, MergeRule{MergeOrder::lww, drop_dead != 0}, stream, table_out, bloom_out);
+}
+
+int cb_tables_scan_lww(const cb_table* const* tables, uint32_t nt, const uint8_t* bounds, const uint64_t* bound_off,
+                       uint32_t nr, int last_unbounded, int drop_dead, uint64_t limit, void* stream, void** out) {
+  if (!out) return fail(CB_EINVAL, "null argument");
+  *out = nullptr;
+  if (int rc = check_range_list(bounds, bound_off, nr, last_unbounded)) return rc;
+  if (limit && nr != 1) return fail(CB_EINVAL, "a limit takes exactly one range");
+  int dev = 0;
+  if (int rc = check_table_list(tables, nt, &dev)) return rc;
+  return scan_ranges(tables, nt, dev, RangeList{bounds, bound_off, nr, last_unbounded != 0}, kScanMaxCuts, limit,
+                     MergeRule{MergeOrder::lww, drop_dead != 0}, (hipStream_t)stream, out);
+}
+
+int cb_tables_count_lww(const cb_table* const* tables, uint32_t nt, const uint8_t* bounds, const uint64_t* bound_off,
+                        uint32_t nr, int last_unbounded, void* stream, uint64_t* entries, uint64_t* live) {
+  if (!entries && !live) return fail(CB_EINVAL, "null argument");
+  if (entries) std::fill(entries, entries + nr, 0);
+  if (live) std::fill(live, live + nr, 0);
+  if (nr)
+    if (int rc = check_range_list(bounds, bound_off, nr, last_unbounded)) return rc;
+  int dev = 0;
+  if (int rc = check_table_list(tables, nt, &dev)) return rc;
+  if (!nr) return CB_OK;
+  return count_ranges(tables, nt, dev, RangeList{bounds, bound_off, nr, last_unbounded != 0}, MergeOrder::lww,
+                      (hipStream_t)stream, entries, live);
 }
 
 int cb_tables_scan_prefixes(const cb_table* const* tables, uint32_t nt, const uint8_t* prefixes,
@@ -699,7 +765,7 @@ int cb_tables_scan_prefixes(const cb_table* const* tables, uint32_t nt, const ui
     return fail(CB_EINVAL, "a prefix without an end before the last one (or prefix offsets that decrease)");
   if (cb::range_list_first_bad(bounds.data(), off.data(), np, last_unbounded) >= 0)
     return fail(CB_EINVAL, "the prefixes are not ascending and disjoint");
-  return scan_ranges(tables, nt, dev, RangeList{bounds.data(), off.data(), np, last_unbounded}, kScanMaxCuts, 0, false,
+  return scan_ranges(tables, nt, dev, RangeList{bounds.data(), off.data(), np, last_unbounded}, kScanMaxCuts, 0, kNewest,
                      (hipStream_t)stream, out);
 }
 
@@ -754,6 +820,25 @@ int cb_scan_which(const void* scan, int32_t* which) {
   if (!r->count || !which) return CB_OK;
   DeviceGuard dg(r->device);
   HIP_TRY(hipMemcpy(which, r->which, r->count * 4, hipMemcpyDefault));
+  return CB_OK;
+}
+
+// The entries' timestamps from their decoded values (k_scan_ts) into a
+// scratch block on the null stream, then copied as cb_scan_which copies (the
+// result was complete when its call returned, so nothing is waited for first).
+int cb_scan_ts(const void* scan, uint64_t* ts) {
+  const cb_scan* r = (const cb_scan*)scan;
+  if (!r) return fail(CB_EINVAL, "null scan");
+  if (!r->count || !ts) return CB_OK;
+  DeviceGuard dg(r->device);
+  note_stream(r->device, nullptr);  // (the pool retires the scratch behind the null stream too)
+  TempBlock tmp{r->device};
+  cb::Carver c;
+  const size_t o_ts = c.take(r->count * 8);
+  if (int rc = tmp.alloc(c, "device allocation failed for a scan's timestamps")) return rc;
+  uint64_t* dts = (uint64_t*)tmp.at(o_ts);
+  HIP_TRY(cb::launch_scan_ts(r->val_off, r->vals, r->count, dts, nullptr));
+  HIP_TRY(hipMemcpy(ts, dts, r->count * 8, hipMemcpyDefault));
   return CB_OK;
 }
 

@@ -16,6 +16,11 @@
 //       variant (the live-row entries) also drops a survivor whose own value
 //       is a tombstone (liverow.hpp); the walk is the same, so a tombstone
 //       still defeats the older lines of its key before it is dropped.
+//   k_compact_ts, k_compact_lww_runs, k_compact_lww_tiles — the select of the
+//       LWW entries in k_compact_select's place (rowts.hpp): every line's
+//       timestamp from its value's text, then per run of equal keys the
+//       decodable line with the greatest timestamp (the run's head lane walks
+//       it once), then the tile sums. Launched for LWW merges only.
 //   k_compact_format — one block per tile: the survivors' offsets from the
 //       scanned tile sums and a block scan, then the block copies the tile's
 //       bytes together, aligned dwords of the output assembled from the
@@ -32,6 +37,7 @@
 #include "launch.hpp"
 #include "liverow.hpp"
 #include "profile.hpp"
+#include "rowts.hpp"
 #include "zone.hpp"
 
 namespace cb {
@@ -111,6 +117,82 @@ __global__ __launch_bounds__(kNT) void k_compact_select(const SortKey* __restric
     }
     slen[p] = len;
   }
+  uint64_t tc, tl, tk;
+  (void)block_scan_sum2<(int)kNT>(len ? 1 : 0, len, kl, &tc, &tl, &tk);
+  if (threadIdx.x == 0) {
+    tcnt[blockIdx.x] = tc;
+    tbytes[blockIdx.x] = tl;
+    tkeys[blockIdx.x] = tk;
+  }
+}
+
+__global__ __launch_bounds__(kNT) void k_compact_ts(const CompactSide* __restrict__ side, uint64_t n,
+                                                    uint64_t* __restrict__ ts) {
+  const uint64_t g = (uint64_t)blockIdx.x * kNT + threadIdx.x;
+  if (g >= n) return;
+  const CompactSide sd = side[g];
+  ts[g] = sd.vdl != kBadValue ? value_ts(sd.src + sd.klen + 1, sd.vdl) : 0;
+}
+
+// The LWW select's first half: one lane per sorted record, and only a lane
+// whose record heads a run (its predecessor names another key: one same_key
+// compare) does anything. It walks forward through its run once, keeps the
+// best decodable record so far (lww_beats; records ascend by input index,
+// which ascends with the table index, so the index breaks ties), writes 0 to
+// slen for every record it passes and, at the run's end, the winner's length
+// over its 0. One writer per run and one visit per record: the work of a run
+// is linear in its length whatever the order of its timestamps, and summed
+// over the runs it is one pass over n records. Only global memory is read, so
+// a run may cross wave, block and tile edges. The other lanes of a head's
+// wave idle while it walks: with a key in t tables one lane in t works, each
+// step two dependent loads (order[q], then side and ts at its index, 8-byte
+// gathers that the sort scattered). Keys in few tables, the common case, walk
+// a step or two.
+template <bool DropDead>
+__global__ __launch_bounds__(kNT) void k_compact_lww_runs(const SortKey* __restrict__ order,
+                                                          const CompactSide* __restrict__ side,
+                                                          const uint64_t* __restrict__ ts,
+                                                          const uint8_t* __restrict__ kb,
+                                                          const uint64_t* __restrict__ ko, uint64_t n,
+                                                          uint64_t* __restrict__ slen) {
+  const uint64_t p = (uint64_t)blockIdx.x * kNT + threadIdx.x;
+  if (p >= n) return;
+  const SortKey a = order[p];
+  if (p && same_key(a, order[p - 1], kb, ko)) return;  // not a run's head
+  bool any = false;
+  uint64_t best = 0, best_ts = 0, best_idx = 0;
+  SortKey b = a;
+  for (uint64_t q = p;;) {
+    const uint32_t vdl = side[b.idx].vdl;
+    if (vdl != kBadValue) {
+      const uint64_t t = ts[b.idx];
+      if (!any || lww_beats(t, b.idx, best_ts, best_idx)) {
+        any = true;
+        best = q;
+        best_ts = t;
+        best_idx = b.idx;
+      }
+    }
+    slen[q] = 0;
+    if (++q >= n) break;
+    b = order[q];
+    if (!same_key(a, b, kb, ko)) break;
+  }
+  if (!any) return;
+  const CompactSide sw = side[best_idx];
+  // (DropDead is a compile-time constant: the plain kernel has no such test)
+  if (!(DropDead && value_dead(sw.vdl))) slen[best] = (uint64_t)sw.llen + 1;
+}
+
+// Its second half: k_compact_select's three tile sums from slen.
+__global__ __launch_bounds__(kNT) void k_compact_lww_tiles(const SortKey* __restrict__ order,
+                                                           const CompactSide* __restrict__ side,
+                                                           const uint64_t* __restrict__ slen, uint64_t n,
+                                                           uint64_t* __restrict__ tcnt, uint64_t* __restrict__ tbytes,
+                                                           uint64_t* __restrict__ tkeys) {
+  const uint64_t p = (uint64_t)blockIdx.x * kNT + threadIdx.x;
+  const uint64_t len = p < n ? slen[p] : 0;
+  const uint64_t kl = len ? side[order[p].idx].klen : 0;
   uint64_t tc, tl, tk;
   (void)block_scan_sum2<(int)kNT>(len ? 1 : 0, len, kl, &tc, &tl, &tk);
   if (threadIdx.x == 0) {
@@ -213,6 +295,30 @@ hipError_t launch_compact_select(const SortKey* order, const CompactSide* side, 
   ProfScope ps(drop_dead ? "k_compact_select_live" : "k_compact_select", s);
   const auto k = drop_dead ? k_compact_select<true> : k_compact_select<false>;
   hipLaunchKernelGGL(k, dim3(blocks_for(n, kNT)), dim3(kNT), 0, s, order, side, kb, ko, n, slen, tcnt, tbytes, tkeys);
+  return hipGetLastError();
+}
+
+hipError_t launch_compact_ts(const CompactSide* side, uint64_t n, uint64_t* ts, hipStream_t s) {
+  if (!n) return hipSuccess;
+  ProfScope ps("k_compact_ts", s);
+  hipLaunchKernelGGL(k_compact_ts, dim3(blocks_for(n, kNT)), dim3(kNT), 0, s, side, n, ts);
+  return hipGetLastError();
+}
+
+hipError_t launch_compact_select_lww(const SortKey* order, const CompactSide* side, const uint64_t* ts,
+                                     const uint8_t* kb, const uint64_t* ko, uint64_t n, bool drop_dead,
+                                     uint64_t* slen, uint64_t* tcnt, uint64_t* tbytes, uint64_t* tkeys,
+                                     hipStream_t s) {
+  if (!n) return hipSuccess;
+  {
+    ProfScope ps(drop_dead ? "k_compact_lww_runs_live" : "k_compact_lww_runs", s);
+    const auto k = drop_dead ? k_compact_lww_runs<true> : k_compact_lww_runs<false>;
+    hipLaunchKernelGGL(k, dim3(blocks_for(n, kNT)), dim3(kNT), 0, s, order, side, ts, kb, ko, n, slen);
+    if (hipError_t e = hipGetLastError()) return e;
+  }
+  ProfScope ps("k_compact_lww_tiles", s);
+  hipLaunchKernelGGL(k_compact_lww_tiles, dim3(blocks_for(n, kNT)), dim3(kNT), 0, s, order, side, slen, n, tcnt,
+                     tbytes, tkeys);
   return hipGetLastError();
 }
 

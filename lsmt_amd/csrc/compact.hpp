@@ -77,6 +77,32 @@ hipError_t launch_compact_gather(const CompactSrc* src, uint32_t nsrc, uint64_t 
 hipError_t launch_compact_select(const SortKey* order, const CompactSide* side, const uint8_t* kb, const uint64_t* ko,
                                  uint64_t n, bool drop_dead, uint64_t* slen, uint64_t* tcnt, uint64_t* tbytes,
                                  uint64_t* tkeys, hipStream_t s);
+
+// Which line of a key a merge keeps. newest: the rule above, by table order
+// alone. lww (the LWW entries): the tables stand for replicas, and the
+// decodable line with the greatest timestamp wins, the lowest table index
+// among equal timestamps (rowts.hpp: the fold of src/cluster.rs:405-416).
+// drop_dead: the winner, whichever order chose it, is then dropped when its
+// value is a tombstone (liverow.hpp); it has defeated the other lines first.
+enum class MergeOrder : uint8_t { newest, lww };
+struct MergeRule {
+  MergeOrder order;
+  bool drop_dead;
+};
+
+// ts[g] = the timestamp of gathered line g (rowts.hpp, from the first 11
+// characters of its value's text); 0 for a line whose value does not decode
+// (never compared). For LWW merges only.
+hipError_t launch_compact_ts(const CompactSide* side, uint64_t n, uint64_t* ts, hipStream_t s);
+// launch_compact_select's outputs under the LWW order, in two launches: per
+// run of equal keys (adjacent in the sorted order, ascending by table index)
+// the one decodable record that lww_beats every other decodable one survives
+// (drop_dead: unless its own value is a tombstone), every other record of the
+// run gets slen 0; then the tile sums of slen.
+hipError_t launch_compact_select_lww(const SortKey* order, const CompactSide* side, const uint64_t* ts,
+                                     const uint8_t* kb, const uint64_t* ko, uint64_t n, bool drop_dead,
+                                     uint64_t* slen, uint64_t* tcnt, uint64_t* tbytes, uint64_t* tkeys,
+                                     hipStream_t s);
 // From the scanned tile sums: the file (out: the survivors' lines `key \t
 // text \n` back to back), its line index without re-reading it (sstable.hpp
 // layout: survivor l is line l of nl; vdl carried over from the input's

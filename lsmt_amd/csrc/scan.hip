@@ -27,12 +27,15 @@
 //       it: one block per tile of sorted records, the survivors and the live
 //       ones (liverow.hpp) summed per run of equal ranges and added to the
 //       ranges' counters. No key is copied and no value read.
+//   k_scan_ts — cb_scan_ts: one lane per entry of a finished result, its
+//       timestamp from its decoded value's first 8 bytes (rowts.hpp).
 #include <hip/hip_runtime.h>
 
 #include "blockscan.hpp"
 #include "launch.hpp"
 #include "liverow.hpp"
 #include "profile.hpp"
+#include "rowts.hpp"
 #include "scan.hpp"
 #include "tablesearch.hpp"
 
@@ -308,6 +311,15 @@ __global__ __launch_bounds__(kNT) void k_scan_count(const SortKey* __restrict__ 
   if (live) atomicAdd((unsigned long long*)(cnt + 2ull * rid + 1), live);
 }
 
+__global__ __launch_bounds__(kNT) void k_scan_ts(const uint64_t* __restrict__ val_off,
+                                                 const uint8_t* __restrict__ vals, uint64_t count,
+                                                 uint64_t* __restrict__ ts) {
+  const uint64_t i = (uint64_t)blockIdx.x * kNT + threadIdx.x;
+  if (i >= count) return;
+  const uint64_t o = val_off[i];
+  ts[i] = decoded_ts(vals + o, val_off[i + 1] - o);
+}
+
 }  // namespace
 
 hipError_t launch_scan_bounds(const ScanTable* tab, uint32_t nt, const ScanRange* rng, uint32_t nr,
@@ -345,6 +357,13 @@ hipError_t launch_scan_count(const SortKey* order, const CompactSide* side, cons
   ProfScope ps("k_scan_count", s);
   hipLaunchKernelGGL(k_scan_count, dim3(blocks_for(n, kNT)), dim3(kNT), 0, s, order, side, slen, src, src_rng, nsrc,
                      n, nr, cnt);
+  return hipGetLastError();
+}
+
+hipError_t launch_scan_ts(const uint64_t* val_off, const uint8_t* vals, uint64_t count, uint64_t* ts, hipStream_t s) {
+  if (!count) return hipSuccess;
+  ProfScope ps("k_scan_ts", s);
+  hipLaunchKernelGGL(k_scan_ts, dim3(blocks_for(count, kNT)), dim3(kNT), 0, s, val_off, vals, count, ts);
   return hipGetLastError();
 }
 

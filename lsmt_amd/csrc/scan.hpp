@@ -95,5 +95,9 @@ hipError_t launch_scan_range_off(const uint32_t* rid, uint64_t count, uint32_t n
 hipError_t launch_scan_count(const SortKey* order, const CompactSide* side, const uint64_t* slen,
                              const CompactSrc* src, const uint32_t* src_rng, uint32_t nsrc, uint64_t n, uint32_t nr,
                              uint64_t* cnt, hipStream_t s);
+// ts[i] = the timestamp (rowts.hpp: split_ts's first half) of entry i of a
+// finished result, from its decoded value vals[val_off[i] .. val_off[i + 1]):
+// 0 below 8 bytes (cb_scan_ts).
+hipError_t launch_scan_ts(const uint64_t* val_off, const uint8_t* vals, uint64_t count, uint64_t* ts, hipStream_t s);
 
 }  // namespace cb
