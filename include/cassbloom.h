@@ -562,6 +562,60 @@ int cb_tables_count_lww(const cb_table* const* tables, uint32_t nt, const uint8_
  * copies. Nothing is written for an empty result; a NULL ts returns CB_OK.
  * Synchronous. */
 int cb_scan_ts(const void* r, uint64_t* ts /* count; host or device, as cb_scan_which */);
+/* ---- rows WHERE column = value: the payload read on the device ----------------
+ * SELECT COUNT(*) of a namespace is live[r] of cb_tables_count only without a
+ * WHERE. With one the reference scans the namespace and, per row
+ * (src/query.rs:309-362): takes the timestamp off the value (split_ts,
+ * src/query.rs:21-27), skips a row without payload, parses the payload as a
+ * JSON object of strings (decode_row, src/schema.rs:42-44: any error gives the
+ * EMPTY map), overlays the key's `|`-separated parts as the key columns, and
+ * compares every condition. The entries below apply that rule; its full text
+ * (the JSON grammar accepted, escapes, UTF-8, duplicate keys) is
+ * lsmt_amd/csrc/rowjson.hpp's, restated from serde_json's documented
+ * behaviour and not run against it.
+ * A predicate is nc conditions, ANDed: condition i is the column name
+ * cols[col_off[i] .. col_off[i+1]), the value vals[val_off[i] .. val_off[i+1])
+ * and part[i], the index of the key column the name is (the caller's schema:
+ * key_columns()), or -1 for a column of the payload. A row's key parts are its
+ * key without its first min(skip, len) bytes, split at every '|'. A row that
+ * is not dead matches when for every i: if 0 <= part[i] < nparts, key part
+ * part[i] equals the value bytewise (the payload is not consulted); else the
+ * payload's map has the name and its last value equals the value bytewise
+ * after unescaping (part[i] >= nparts falls back to the payload too). nc == 0:
+ * every live row matches. A row whose conditions are all answered by its key
+ * matches even when its payload is not JSON.
+ * CB_EINVAL from all three entries, checked before the table list or result
+ * is looked at, outputs cleared: w NULL; a NULL pointer next to a non-zero nc;
+ * offsets that decrease; nc > 16; more than 4096 bytes of names and values
+ * together; part[i] < -1 or > 255; a NULL `matched` / `flags` / `out`. Empty
+ * names and empty values are legal. `w` is a const cb_where*. */
+typedef struct cb_where {        /* host memory; conditions are ANDed */
+  const uint8_t* cols; const uint64_t* col_off;  /* nc+1, non-decreasing */
+  const uint8_t* vals; const uint64_t* val_off;  /* nc+1 */
+  const int32_t* part;                            /* nc: key part index, or -1 */
+  uint32_t nc;
+} cb_where;
+/* cb_tables_count's call (range lists, cut cap, refusals, one wait) with the
+ * matching rows counted beside the live ones: live[r] is exactly
+ * cb_tables_count's (lww != 0: cb_tables_count_lww's), matched[r] the number
+ * of matching rows among them, the key parts of range r taken after skip[r]
+ * bytes. The reference's COUNT(*) WHERE of namespace ns is the prefix
+ * ns + ":" with skip = len(ns) + 1. No result is allocated and no value
+ * decoded into memory: each surviving live line's value text is read in place. */
+int cb_tables_count_where(const cb_table* const* tables, uint32_t nt, const uint8_t* bounds,
+                          const uint64_t* bound_off, uint32_t nr, int last_unbounded,
+                          const uint32_t* skip /* nr, nullable = zeros */, const void* w /* cb_where */, int lww,
+                          void* stream, uint64_t* live /* nr, nullable */, uint64_t* matched /* nr */);
+/* flags[i] = 1 when entry i of a result of any cb_tables_scan* call matches,
+ * else 0 (dead entries: 0), over the decoded values the result holds; skip is
+ * per range of the result (cb_scan_ranges). flags: count bytes, host or device
+ * memory. Nothing is written for an empty result. Synchronous, as cb_scan_ts. */
+int cb_scan_match(const void* r, const uint32_t* skip /* one per range of r, nullable */,
+                  const void* w /* cb_where */, uint8_t* flags /* count; host or device, as cb_scan_which */);
+/* Host only, no device: the rule for one row, e.g. a memtable row, which the
+ * store merges over the tables' answer as it does for get. *out = 1 or 0. */
+int cb_row_matches(const uint8_t* key, uint64_t key_len, uint32_t skip, const uint8_t* value,
+                   uint64_t value_len, const void* w /* cb_where */, int* out);
 /* Finalise a table from cb_sstable_create*: wait for its work, take its
  * results; returns its deferred error, if any. Idempotent, thread-safe. */
 int cb_table_wait(const cb_table* t);

@@ -162,6 +162,9 @@ def load():
         "cb_tables_scan_lww": ([P, u32, u8p, P, u32, i32, i32, u64, P, pp], i32),
         "cb_tables_count_lww": ([P, u32, u8p, P, u32, i32, P, P, P], i32),
         "cb_scan_ts": ([P, P], i32),
+        "cb_tables_count_where": ([P, u32, u8p, P, u32, i32, P, P, i32, P, P, P], i32),
+        "cb_scan_match": ([P, P, P, P], i32),
+        "cb_row_matches": ([u8p, u64, u32, u8p, u64, P, ctypes.POINTER(i32)], i32),
         "cb_scan_ranges": ([P, pu64, P], i32),
         "cb_key_prefix_end": ([u8p, u64, u8p, pu64, ctypes.POINTER(i32)], i32),
         "cb_scan_info": ([P, pu64, pu64, pu64, ctypes.POINTER(i32)], i32),

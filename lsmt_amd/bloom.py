@@ -933,6 +933,23 @@ class ScanResult:
         self.copy_ts(t)
         return t[:self.count]
 
+    def copy_match(self, flags, where, key_columns=(), skip=None) -> None:
+        """match()'s verdicts as bytes (0 / 1) into a numpy array or device
+        tensor of `count` uint8."""
+        w = _Where(where, key_columns)
+        sk = None if skip is None else np.ascontiguousarray(_per_range(skip, self.nranges), np.uint32)
+        check(_L().cb_scan_match(self._h, _ptr_of(sk)[0], w.ref(), _ptr_of(flags)[0]))
+
+    def match(self, where, key_columns=(), skip=None) -> np.ndarray:
+        """bool[count]: which entries are rows that match `where` (count_where's
+        rule, cb_scan_match): a filtered select over a result that is already
+        on the device. Dead entries are False. skip: the bytes of each key
+        before its `|`-separated parts, one number for all ranges or one per
+        range (default 0)."""
+        f = np.zeros(max(self.count, 1), np.uint8)
+        self.copy_match(f, where, key_columns, skip)
+        return f[:self.count].astype(bool)
+
     def items(self) -> "list[tuple[bytes, bytes]]":
         return list(zip(self.keys(), self.values()))
 
@@ -1143,6 +1160,81 @@ def count_lww(tables: Sequence[Table], ranges=None, prefixes=None, stream=None):
     _raise(_L().cb_tables_count_lww(arr, len(tables), data, _ptr_of(off)[0], nr, last_unbounded, _stream(stream),
                                     _ptr_of(entries)[0], _ptr_of(live)[0]))
     return entries[:nr], live[:nr]
+
+
+class _CbWhere(ctypes.Structure):
+    """cb_where (include/cassbloom.h)."""
+    _fields_ = [("cols", ctypes.c_void_p), ("col_off", ctypes.c_void_p), ("vals", ctypes.c_void_p),
+                ("val_off", ctypes.c_void_p), ("part", ctypes.c_void_p), ("nc", ctypes.c_uint32)]
+
+
+class _Where:
+    """A cb_where built from a mapping or a list of (column, value), with
+    `key_columns` (the schema's key_columns(), src/schema.rs:27-33) giving each
+    condition its key part; keeps the arrays it points into alive."""
+
+    def __init__(self, where, key_columns=()):
+        pairs = list(where.items()) if hasattr(where, "items") else list(where)
+        cols = [_key_bytes(c) for c, _ in pairs]
+        vals = [_key_bytes(v) for _, v in pairs]
+        kc = [_key_bytes(c) for c in key_columns]
+        self.col_off = np.zeros(len(pairs) + 1, np.uint64)
+        self.val_off = np.zeros(len(pairs) + 1, np.uint64)
+        np.cumsum([len(c) for c in cols], out=self.col_off[1:])
+        np.cumsum([len(v) for v in vals], out=self.val_off[1:])
+        self.cols = ctypes.create_string_buffer(b"".join(cols), max(int(self.col_off[-1]), 1))
+        self.vals = ctypes.create_string_buffer(b"".join(vals), max(int(self.val_off[-1]), 1))
+        self.part = np.array([kc.index(c) if c in kc else -1 for c in cols] + [0], np.int32)
+        self.c = _CbWhere(ctypes.addressof(self.cols), self.col_off.ctypes.data, ctypes.addressof(self.vals),
+                          self.val_off.ctypes.data, self.part.ctypes.data, len(pairs))
+
+    def ref(self):
+        return ctypes.addressof(self.c)
+
+
+def _per_range(skip, nr: int) -> "list[int]":
+    if isinstance(skip, (int, np.integer)):
+        return [int(skip)] * nr
+    skip = [int(x) for x in skip]
+    if len(skip) != nr:
+        raise ValueError("one skip per range")
+    return skip
+
+
+def count_where(tables: Sequence[Table], where, key_columns=(), ranges=None, prefixes=None, skip=None,
+                lww: bool = False, stream=None):
+    """Per range, the live rows (count()'s live, or count_lww()'s with lww)
+    and how many of them match `where`, without building a result
+    (cb_tables_count_where): (live, matched), two uint64 arrays. `where` is a
+    mapping or a list of (column, value), all ANDed; a column named in
+    `key_columns` is compared with that `|`-separated part of the key after
+    its first `skip` bytes, every other one with the row's JSON payload, the
+    value after its 8-byte timestamp, parsed as the reference's decode_row
+    parses it (src/schema.rs:42-44; any error: no columns). SELECT COUNT(*)
+    FROM ns WHERE ... (src/query.rs:309-362) is prefixes=[ns + ":"], whose
+    skip defaults to the prefix's length; with ranges it defaults to 0. skip
+    may be one number or one per range."""
+    data, off, nr, last_unbounded = _range_list(ranges, prefixes)
+    arr, _ = _table_list(tables)
+    w = _Where(where, key_columns)
+    if skip is None:
+        skip = [len(_key_bytes(p)) for p in prefixes] if prefixes is not None else 0
+    sk = np.ascontiguousarray(_per_range(skip, nr) + [0], np.uint32)
+    live, matched = np.zeros(max(nr, 1), np.uint64), np.zeros(max(nr, 1), np.uint64)
+    _raise(_L().cb_tables_count_where(arr, len(tables), data, _ptr_of(off)[0], nr, last_unbounded, _ptr_of(sk)[0],
+                                      w.ref(), int(bool(lww)), _stream(stream), _ptr_of(live)[0],
+                                      _ptr_of(matched)[0]))
+    return live[:nr], matched[:nr]
+
+
+def row_matches(key, value, where, key_columns=(), skip: int = 0) -> bool:
+    """count_where's rule for one row on the host (cb_row_matches; no device):
+    e.g. a memtable row, which a store merges over the tables' answer."""
+    k, v = _key_bytes(key), _key_bytes(value)
+    w = _Where(where, key_columns)
+    out = ctypes.c_int()
+    check(_L().cb_row_matches(k, len(k), int(skip), v, len(v), w.ref(), ctypes.byref(out)))
+    return bool(out.value)
 
 
 def _to_var(b: KeyBatch) -> KeyBatch:

@@ -9,7 +9,9 @@
 // (cb_tables_compact_lww, cb_tables_scan_lww, cb_tables_count_lww) run them
 // with the select that keeps a key's line of the greatest timestamp
 // (rowts.hpp) in place of its newest one; cb_scan_ts reads the timestamps of
-// any result.
+// any result. The WHERE entries (cb_tables_count_where, cb_scan_match,
+// cb_row_matches) apply the row rule (rowjson.hpp): the count with a tail
+// kernel that reads every live survivor's payload in place.
 //
 // Reference: src/sstable.rs:51-98 (the file a compaction writes),
 // src/lib.rs:125-146 (Database::get, whose answers both reproduce), src/cluster.rs:405-416,
@@ -531,8 +533,18 @@ int scan_ranges(const cb_table* const* tables, uint32_t nt, int dev, const Range
 // entries / live: host, nr words each, either nullable, zeroed by the caller.
 // order: which line of a key is its entry (cb_tables_count_lww: the winner by
 // timestamp); no order drops anything here, live is counted beside entries.
+// where (nullable; cb_tables_count_where): the tail is k_scan_count_where in
+// place of k_scan_count, with a third counter per range, matched (host, nr
+// words, zeroed by the caller). The predicate and the ranges' skips travel as
+// one small block, staged before the cuts so that the cuts' first wait covers
+// it (the source is pageable): the call waits no more often than a count.
+struct WhereCall {
+  cb::WherePred pred;
+  const uint32_t* skip;  // nr, or nullptr
+};
 int count_ranges(const cb_table* const* tables, uint32_t nt, int dev, const RangeList& rl, MergeOrder order,
-                 hipStream_t s, uint64_t* entries, uint64_t* live) {
+                 hipStream_t s, uint64_t* entries, uint64_t* live, const WhereCall* where = nullptr,
+                 uint64_t* matched = nullptr) {
   ScanInput in;
   bool nothing = false;
   if (int rc = scan_input(tables, nt, rl, kScanMaxCuts, &in, &nothing)) return rc;
@@ -541,33 +553,65 @@ int count_ranges(const cb_table* const* tables, uint32_t nt, int dev, const Rang
   if (rc) return rc;
   DeviceGuard dg(dev);
   (void)workspace(dev, s);  // (registers s: the pool retires blocks behind it)
-  TempBlock cuts{dev}, tmp{dev}, cnt{dev};
+  TempBlock cuts{dev}, tmp{dev}, cnt{dev}, pred{dev};
+  const cb::WherePred* dpred = nullptr;
+  const uint32_t* dskip = nullptr;
+  std::vector<uint8_t> up;  // (lives until the call's last wait)
+  if (where) {
+    cb::Carver pc;
+    const size_t o_pred = pc.take(sizeof(cb::WherePred)), o_skip = pc.take(where->skip ? rl.nr * 4ull : 0);
+    if ((rc = pred.alloc(pc, "device allocation failed for a count's predicate"))) return rc;
+    up.assign(pc.total(), 0);
+    std::memcpy(&up[o_pred], &where->pred, sizeof(cb::WherePred));
+    if (where->skip) std::memcpy(&up[o_skip], where->skip, rl.nr * 4ull);
+    HIP_TRY(hipMemcpyAsync(pred.p, up.data(), up.size(), hipMemcpyHostToDevice, s));
+    dpred = (const cb::WherePred*)pred.at(o_pred);
+    if (where->skip) dskip = (const uint32_t*)pred.at(o_skip);
+  }
   ScanCuts c;
-  if ((rc = cut_tables(in.tabs, in.all_lines, in.all_bytes, rl, cuts, s, &c))) return rc;
+  if ((rc = cut_tables(in.tabs, in.all_lines, in.all_bytes, rl, cuts, s, &c))) {
+    if (where) (void)hipStreamSynchronize(s);  // (a refusal before the cuts' first wait: `up` is still being read)
+    return rc;
+  }
   if (!c.n) return CB_OK;
   Merge mg;
   if ((rc = merge_alloc(0, c.n, c.kbound, order, tmp, &mg))) return rc;
   cb::Carver cc;
-  const size_t words = 2 * (size_t)rl.nr, o_cnt = cc.take(words * 8);
+  const size_t per = where ? 3 : 2, words = per * (size_t)rl.nr, o_cnt = cc.take(words * 8);
   if ((rc = cnt.alloc(cc, "device allocation failed for a count's counters"))) return rc;
   uint64_t* dcnt = (uint64_t*)cnt.at(o_cnt);
   if ((rc = enqueue_merge_select(mg, c.dsrc, c.nsrc, MergeRule{order, false}, s))) return rc;
   HIP_TRY(hipMemsetAsync(dcnt, 0, words * 8, s));
-  HIP_TRY(cb::launch_scan_count(mg.order, mg.side, mg.slen, c.dsrc, c.drng, c.nsrc, mg.n, rl.nr, dcnt, s));
+  if (where)
+    HIP_TRY(cb::launch_scan_count_where(mg.order, mg.side, mg.slen, c.dsrc, c.drng, c.nsrc, mg.n, rl.nr, dpred, dskip,
+                                        dcnt, s));
+  else
+    HIP_TRY(cb::launch_scan_count(mg.order, mg.side, mg.slen, c.dsrc, c.drng, c.nsrc, mg.n, rl.nr, dcnt, s));
   std::vector<uint64_t> h(words, 0);
   HIP_TRY(hipMemcpyAsync(h.data(), dcnt, words * 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   uint64_t all = 0;
   bool ok = true;
   for (uint32_t r = 0; ok && r < rl.nr; ++r) {
-    ok = h[2 * r] <= c.n - all && h[2 * r + 1] <= h[2 * r];
-    all += h[2 * r];
+    ok = h[per * r] <= c.n - all && h[per * r + 1] <= h[per * r] && (!where || h[per * r + 2] <= h[per * r + 1]);
+    all += h[per * r];
   }
   if (!ok) return fail(CB_EHIP, "count: inconsistent counters");
   for (uint32_t r = 0; r < rl.nr; ++r) {
-    if (entries) entries[r] = h[2 * r];
-    if (live) live[r] = h[2 * r + 1];
+    if (entries) entries[r] = h[per * r];
+    if (live) live[r] = h[per * r + 1];
+    if (where) matched[r] = h[per * r + 2];
   }
+  return CB_OK;
+}
+
+// A cb_where checked and packed (rowjson.hpp): the three WHERE entries' first step.
+int take_where(const void* where, cb::WherePred* pred) {
+  const cb_where* w = (const cb_where*)where;
+  if (!w) return fail(CB_EINVAL, "null predicate");
+  if (const char* why = cb::where_check(w->cols, w->col_off, w->vals, w->val_off, w->part, w->nc))
+    return fail(CB_EINVAL, why);
+  cb::where_pack(w->cols, w->col_off, w->vals, w->val_off, w->part, w->nc, pred);
   return CB_OK;
 }
 
@@ -745,6 +789,74 @@ int cb_tables_count_lww(const cb_table* const* tables, uint32_t nt, const uint8_
   if (!nr) return CB_OK;
   return count_ranges(tables, nt, dev, RangeList{bounds, bound_off, nr, last_unbounded != 0}, MergeOrder::lww,
                       (hipStream_t)stream, entries, live);
+}
+
+// cb_tables_count with the predicate's tail kernel. The live-row entries'
+// order: the call's own arguments first, outputs cleared on every refusal.
+int cb_tables_count_where(const cb_table* const* tables, uint32_t nt, const uint8_t* bounds, const uint64_t* bound_off,
+                          uint32_t nr, int last_unbounded, const uint32_t* skip, const void* w, int lww, void* stream,
+                          uint64_t* live, uint64_t* matched) {
+  if (live) std::fill(live, live + nr, 0);
+  if (!matched) return fail(CB_EINVAL, "null argument");
+  std::fill(matched, matched + nr, 0);
+  auto wc = std::make_unique<WhereCall>();
+  wc->skip = skip;
+  if (int rc = take_where(w, &wc->pred)) return rc;
+  if (nr)
+    if (int rc = check_range_list(bounds, bound_off, nr, last_unbounded)) return rc;
+  int dev = 0;
+  if (int rc = check_table_list(tables, nt, &dev)) return rc;
+  if (!nr) return CB_OK;
+  return count_ranges(tables, nt, dev, RangeList{bounds, bound_off, nr, last_unbounded != 0},
+                      lww ? MergeOrder::lww : MergeOrder::newest, (hipStream_t)stream, nullptr, live, wc.get(), matched);
+}
+
+// The verdicts of a finished result's entries (k_scan_match) into a scratch
+// block on the null stream, then copied as cb_scan_ts copies. The predicate,
+// the ranges' offsets and skips travel in the same block.
+int cb_scan_match(const void* scan, const uint32_t* skip, const void* w, uint8_t* flags) {
+  const cb_scan* r = (const cb_scan*)scan;
+  auto pred = std::make_unique<cb::WherePred>();
+  if (!flags) return fail(CB_EINVAL, "null argument");
+  if (int rc = take_where(w, pred.get())) return rc;
+  if (!r) return fail(CB_EINVAL, "null scan");
+  if (!r->count) return CB_OK;
+  DeviceGuard dg(r->device);
+  note_stream(r->device, nullptr);  // (the pool retires the scratch behind the null stream too)
+  TempBlock tmp{r->device};
+  const size_t nro = r->range_off.size(), nr = nro - 1;
+  cb::Carver c;
+  const size_t o_pred = c.take(sizeof(cb::WherePred)), o_roff = c.take(skip ? nro * 8 : 0),
+               o_skip = c.take(skip ? nr * 4 : 0);
+  const size_t up_bytes = c.total();
+  const size_t o_flags = c.take(r->count);
+  if (int rc = tmp.alloc(c, "device allocation failed for a scan's verdicts")) return rc;
+  std::vector<uint8_t> up(up_bytes, 0);
+  std::memcpy(&up[o_pred], pred.get(), sizeof(cb::WherePred));
+  if (skip) {
+    std::memcpy(&up[o_roff], r->range_off.data(), nro * 8);
+    std::memcpy(&up[o_skip], skip, nr * 4);
+  }
+  HIP_TRY(hipMemcpy(tmp.p, up.data(), up_bytes, hipMemcpyHostToDevice));
+  uint8_t* dflags = tmp.at(o_flags);
+  HIP_TRY(cb::launch_scan_match(r->key_off, r->keys, r->val_off, r->vals, r->count,
+                                skip ? (const uint64_t*)tmp.at(o_roff) : nullptr,
+                                skip ? (const uint32_t*)tmp.at(o_skip) : nullptr, (uint32_t)nr,
+                                (const cb::WherePred*)tmp.at(o_pred), dflags, nullptr));
+  HIP_TRY(hipMemcpy(flags, dflags, r->count, hipMemcpyDefault));
+  return CB_OK;
+}
+
+int cb_row_matches(const uint8_t* key, uint64_t key_len, uint32_t skip, const uint8_t* value, uint64_t value_len,
+                   const void* w, int* out) {
+  if (!out) return fail(CB_EINVAL, "null argument");
+  *out = 0;
+  auto pred = std::make_unique<cb::WherePred>();
+  if (int rc = take_where(w, pred.get())) return rc;
+  if ((key_len && !key) || (value_len && !value)) return fail(CB_EINVAL, "null key or value with a length");
+  cb::DecodedBytes v(value, value_len);
+  *out = cb::row_matches(*pred, key, key_len, skip, v) ? 1 : 0;
+  return CB_OK;
 }
 
 int cb_tables_scan_prefixes(const cb_table* const* tables, uint32_t nt, const uint8_t* prefixes,

@@ -29,12 +29,20 @@
 //       ranges' counters. No key is copied and no value read.
 //   k_scan_ts — cb_scan_ts: one lane per entry of a finished result, its
 //       timestamp from its decoded value's first 8 bytes (rowts.hpp).
+//   k_scan_count_where — cb_tables_count_where's tail, k_scan_count's shape
+//       with a third sum: a lane whose record is a live survivor runs the row
+//       rule (rowjson.hpp) over its line, the key in place and the value's
+//       base64 text decoded on the fly, one aligned dword per three bytes.
+//       One lane per row: a tile takes as long as its longest payload.
+//   k_scan_match — cb_scan_match: one lane per entry of a finished result,
+//       the same rule over its key and its decoded value.
 #include <hip/hip_runtime.h>
 
 #include "blockscan.hpp"
 #include "launch.hpp"
 #include "liverow.hpp"
 #include "profile.hpp"
+#include "rowjson.hpp"
 #include "rowts.hpp"
 #include "scan.hpp"
 #include "tablesearch.hpp"
@@ -320,6 +328,97 @@ __global__ __launch_bounds__(kNT) void k_scan_ts(const uint64_t* __restrict__ va
   ts[i] = decoded_ts(vals + o, val_off[i + 1] - o);
 }
 
+// Four characters of a value's text in a table's file by aligned dword
+// loads (rowjson.hpp's Text policy): the text starts anywhere, so a quantum
+// straddles two dwords, and the second is kept for the next quantum. The
+// dword after the last character lies in the file's 16 bytes of slack at the
+// latest, the one before the first in the line itself.
+struct TextByDwords {
+  const uint32_t* wp;
+  uint32_t sh, cw;
+  uint64_t cq;
+  __device__ explicit TextByDwords(const uint8_t* t)
+      : wp(reinterpret_cast<const uint32_t*>(t - ((uintptr_t)t & 3))), sh(8 * (uint32_t)((uintptr_t)t & 3)), cw(0), cq(~0ull) {}
+  __device__ uint32_t quad(uint64_t q) {
+    const uint32_t lo = q == cq ? cw : wp[q];
+    if (!sh) return lo;
+    const uint32_t hi = wp[q + 1];
+    cq = q + 1;
+    cw = hi;
+    return lo >> sh | hi << (32 - sh);
+  }
+};
+
+// k_scan_count with the matched rows beside the entries and the live ones:
+// three flags packed 21 bits apart (none passes 256), cnt[3 r ..] = {entries,
+// live, matched} of range r. Every lane reaches the block scan; only the
+// lanes of live survivors read their lines.
+__global__ __launch_bounds__(kNT) void k_scan_count_where(const SortKey* __restrict__ order,
+                                                          const CompactSide* __restrict__ side,
+                                                          const uint64_t* __restrict__ slen,
+                                                          const CompactSrc* __restrict__ src,
+                                                          const uint32_t* __restrict__ src_rng, uint32_t nsrc,
+                                                          uint64_t n, uint32_t nr, const WherePred* __restrict__ w,
+                                                          const uint32_t* __restrict__ skip,
+                                                          uint64_t* __restrict__ cnt) {
+  constexpr uint32_t kPast = 0xFFFFFFFFu;
+  constexpr uint32_t kField = 21;
+  __shared__ uint32_t s_rid[kNT + 1];
+  __shared__ uint64_t s_inc[kNT];
+  const uint32_t t = threadIdx.x;
+  const uint64_t p = (uint64_t)blockIdx.x * kNT + t;
+  uint32_t rid = kPast;
+  uint64_t v = 0;
+  if (p < n) {
+    const uint32_t g = order[p].idx;
+    rid = nr > 1 ? src_rng[src_of(src, nsrc, g)] : 0;  // (uniform)
+    if (slen[p]) {
+      const CompactSide sd = side[g];
+      v = 1;
+      if (!value_dead(sd.vdl)) {
+        v |= 1ull << kField;
+        B64Bytes<TextByDwords> value(TextByDwords(sd.src + sd.klen + 1), sd.vdl);
+        if (row_matches(*w, sd.src, sd.klen, skip && rid < nr ? skip[rid] : 0u, value)) v |= 1ull << 2 * kField;
+      }
+    }
+  }
+  uint64_t total;
+  const uint64_t inc = block_scan<(int)kNT>(v, &total) + v;
+  s_rid[t] = rid;
+  s_inc[t] = inc;
+  if (t == 0) s_rid[kNT] = kPast;
+  __syncthreads();
+  if (p >= n || s_rid[t + 1] == rid || rid >= nr) return;  // not the end of a run
+  uint32_t lo = 0, hi = t;  // s_rid[i] < rid for i < lo, s_rid[hi] == rid
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (s_rid[mid] < rid) lo = mid + 1;
+    else hi = mid;
+  }
+  const uint64_t sum = inc - (lo ? s_inc[lo - 1] : 0);
+  constexpr uint64_t kMask = (1ull << kField) - 1;
+  const unsigned long long entries = sum & kMask, live = sum >> kField & kMask, matched = sum >> 2 * kField;
+  if (entries) atomicAdd((unsigned long long*)(cnt + 3ull * rid), entries);
+  if (live) atomicAdd((unsigned long long*)(cnt + 3ull * rid + 1), live);
+  if (matched) atomicAdd((unsigned long long*)(cnt + 3ull * rid + 2), matched);
+}
+
+__global__ __launch_bounds__(kNT) void k_scan_match(const uint64_t* __restrict__ key_off,
+                                                    const uint8_t* __restrict__ keys,
+                                                    const uint64_t* __restrict__ val_off,
+                                                    const uint8_t* __restrict__ vals, uint64_t count,
+                                                    const uint64_t* __restrict__ range_off,
+                                                    const uint32_t* __restrict__ skip, uint32_t nr,
+                                                    const WherePred* __restrict__ w, uint8_t* __restrict__ flags) {
+  const uint64_t i = (uint64_t)blockIdx.x * kNT + threadIdx.x;
+  if (i >= count) return;
+  uint32_t sk = 0;
+  if (skip) sk = skip[last_le(nr, i, [&](uint32_t r) { return range_off[r]; })];  // the entry's range (range_off[0] = 0)
+  const uint64_t ko = key_off[i], vo = val_off[i];
+  DecodedBytes value(vals + vo, val_off[i + 1] - vo);
+  flags[i] = row_matches(*w, keys + ko, key_off[i + 1] - ko, sk, value) ? 1 : 0;
+}
+
 }  // namespace
 
 hipError_t launch_scan_bounds(const ScanTable* tab, uint32_t nt, const ScanRange* rng, uint32_t nr,
@@ -364,6 +463,27 @@ hipError_t launch_scan_ts(const uint64_t* val_off, const uint8_t* vals, uint64_t
   if (!count) return hipSuccess;
   ProfScope ps("k_scan_ts", s);
   hipLaunchKernelGGL(k_scan_ts, dim3(blocks_for(count, kNT)), dim3(kNT), 0, s, val_off, vals, count, ts);
+  return hipGetLastError();
+}
+
+hipError_t launch_scan_count_where(const SortKey* order, const CompactSide* side, const uint64_t* slen,
+                                   const CompactSrc* src, const uint32_t* src_rng, uint32_t nsrc, uint64_t n,
+                                   uint32_t nr, const WherePred* w, const uint32_t* skip, uint64_t* cnt,
+                                   hipStream_t s) {
+  if (!n || !nr) return hipSuccess;
+  ProfScope ps("k_scan_count_where", s);
+  hipLaunchKernelGGL(k_scan_count_where, dim3(blocks_for(n, kNT)), dim3(kNT), 0, s, order, side, slen, src, src_rng,
+                     nsrc, n, nr, w, skip, cnt);
+  return hipGetLastError();
+}
+
+hipError_t launch_scan_match(const uint64_t* key_off, const uint8_t* keys, const uint64_t* val_off,
+                             const uint8_t* vals, uint64_t count, const uint64_t* range_off, const uint32_t* skip,
+                             uint32_t nr, const WherePred* w, uint8_t* flags, hipStream_t s) {
+  if (!count) return hipSuccess;
+  ProfScope ps("k_scan_match", s);
+  hipLaunchKernelGGL(k_scan_match, dim3(blocks_for(count, kNT)), dim3(kNT), 0, s, key_off, keys, val_off, vals, count,
+                     range_off, skip, nr, w, flags);
   return hipGetLastError();
 }
 

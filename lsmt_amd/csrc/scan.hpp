@@ -21,6 +21,7 @@
 
 #include "compact.hpp"
 #include "flush.hpp"
+#include "rowjson.hpp"
 #include "sstable.hpp"
 
 namespace cb {
@@ -99,5 +100,20 @@ hipError_t launch_scan_count(const SortKey* order, const CompactSide* side, cons
 // finished result, from its decoded value vals[val_off[i] .. val_off[i + 1]):
 // 0 below 8 bytes (cb_scan_ts).
 hipError_t launch_scan_ts(const uint64_t* val_off, const uint8_t* vals, uint64_t count, uint64_t* ts, hipStream_t s);
+// launch_scan_count with a predicate (cb_tables_count_where): cnt[3 r] and
+// cnt[3 r + 1] as launch_scan_count's two, cnt[3 r + 2] += the live ones whose
+// row matches w (rowjson.hpp), the key's parts taken after skip[r] bytes
+// (skip nullable: zeros). The caller zeroes cnt (3 nr words). A live
+// survivor's value text is read in place, at side[g].src + klen + 1.
+hipError_t launch_scan_count_where(const SortKey* order, const CompactSide* side, const uint64_t* slen,
+                                   const CompactSrc* src, const uint32_t* src_rng, uint32_t nsrc, uint64_t n,
+                                   uint32_t nr, const WherePred* w, const uint32_t* skip, uint64_t* cnt,
+                                   hipStream_t s);
+// flags[i] = whether entry i of a finished result matches w (cb_scan_match),
+// 0 for a dead entry. skip (nullable: zeros) is per range, and range_off
+// (nr + 1 offsets, device; read only with skip) says which range an entry is of.
+hipError_t launch_scan_match(const uint64_t* key_off, const uint8_t* keys, const uint64_t* val_off,
+                             const uint8_t* vals, uint64_t count, const uint64_t* range_off, const uint32_t* skip,
+                             uint32_t nr, const WherePred* w, uint8_t* flags, hipStream_t s);
 
 }  // namespace cb
