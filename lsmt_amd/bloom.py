@@ -817,20 +817,10 @@ def compact(tables: Sequence[Table], m: int = 1024, stream=None):
     and a key whose value decodes nowhere is dropped. Returns (Table,
     BloomFilter of m bits, ZoneMap), as sstable_create does. The inputs are
     not modified and may be closed as soon as the call returns."""
-    if not tables:
-        arr, dev = None, 0
-    else:
-        arr = (ctypes.c_void_p * len(tables))(*[t._h.value for t in tables])
-        dev = tables[0].device
+    arr, dev = _table_list(tables)
     th, fh = ctypes.c_void_p(), ctypes.c_void_p()
-    _raise(_L().cb_tables_compact(ctypes.cast(arr, ctypes.c_void_p) if arr is not None else None, len(tables), int(m),
-                                  _stream(stream), ctypes.byref(th), ctypes.byref(fh)))
-    table = Table._adopt(th.value, dev)
-    bloom = BloomFilter(0, device=dev, _handle=fh.value)
-    zone = ZoneMap()
-    if table.nlines:
-        zone = ZoneMap(table._zone(0), table._zone(1))
-    return table, bloom, zone
+    _raise(_L().cb_tables_compact(arr, len(tables), int(m), _stream(stream), ctypes.byref(th), ctypes.byref(fh)))
+    return _adopt_compaction(th, fh, dev)
 
 
 def _key_bytes(k) -> bytes:
@@ -975,11 +965,7 @@ def scan(tables: Sequence[Table], lo=b"", hi=None, prefix=None, limit: int = 0, 
     closed as soon as the call returns."""
     if prefix is not None and (hi is not None or _key_bytes(lo)):
         raise ValueError("prefix excludes lo and hi")
-    if not tables:
-        arr, dev = None, 0
-    else:
-        arr = ctypes.cast((ctypes.c_void_p * len(tables))(*[t._h.value for t in tables]), ctypes.c_void_p)
-        dev = tables[0].device
+    arr, dev = _table_list(tables)
     h = ctypes.c_void_p()
     if prefix is not None:
         p = _key_bytes(prefix)
@@ -1007,30 +993,21 @@ def scan_many(tables: Sequence[Table], ranges=None, prefixes=None, stream=None) 
     prefixes=[ns + ":" for ns in sorted(names)]."""
     if (ranges is None) == (prefixes is None):
         raise ValueError("exactly one of ranges and prefixes")
-    if not tables:
-        arr, dev = None, 0
-    else:
-        arr = ctypes.cast((ctypes.c_void_p * len(tables))(*[t._h.value for t in tables]), ctypes.c_void_p)
-        dev = tables[0].device
+    arr, dev = _table_list(tables)
     h = ctypes.c_void_p()
-    if prefixes is not None:
+    if prefixes is not None:  # (the library turns them into ranges itself)
         parts = [_key_bytes(p) for p in prefixes]
-        last_unbounded = 0
+        off = np.zeros(len(parts) + 1, np.uint64)
+        np.cumsum([len(b) for b in parts], out=off[1:])
+        _raise(_L().cb_tables_scan_prefixes(arr, len(tables), b"".join(parts), _ptr_of(off)[0], len(parts),
+                                            _stream(stream), ctypes.byref(h)))
     else:
-        pairs = [(_key_bytes(lo), hi) for lo, hi in ranges]
-        if any(hi is None for _, hi in pairs[:-1]):
+        ranges = list(ranges)
+        if any(hi is None for _, hi in ranges[:-1]):
             raise ValueError("hi=None is allowed on the last range only")
-        last_unbounded = int(bool(pairs) and pairs[-1][1] is None)
-        parts = [b for lo, hi in pairs for b in (lo, _key_bytes(hi) if hi is not None else b"")]
-    off = np.zeros(len(parts) + 1, np.uint64)
-    np.cumsum([len(b) for b in parts], out=off[1:])
-    data = b"".join(parts)
-    if prefixes is not None:
-        _raise(_L().cb_tables_scan_prefixes(arr, len(tables), data, _ptr_of(off)[0], len(parts), _stream(stream),
-                                            ctypes.byref(h)))
-    else:
-        _raise(_L().cb_tables_scan_many(arr, len(tables), data, _ptr_of(off)[0], len(parts) // 2, last_unbounded,
-                                        _stream(stream), ctypes.byref(h)))
+        data, off, nr, last_unbounded = _range_list(ranges, None)
+        _raise(_L().cb_tables_scan_many(arr, len(tables), data, _ptr_of(off)[0], nr, last_unbounded, _stream(stream),
+                                        ctypes.byref(h)))
     return ScanResult(h.value, dev)
 
 
@@ -1056,6 +1033,16 @@ def _table_list(tables: Sequence[Table]):
     if not tables:
         return None, 0
     return ctypes.cast((ctypes.c_void_p * len(tables))(*[t._h.value for t in tables]), ctypes.c_void_p), tables[0].device
+
+
+def _adopt_compaction(th, fh, dev: int):
+    """(Table, BloomFilter, ZoneMap) of the handles a compaction entry returned."""
+    table = Table._adopt(th.value, dev)
+    bloom = BloomFilter(0, device=dev, _handle=fh.value)
+    zone = ZoneMap()
+    if table.nlines:
+        zone = ZoneMap(table._zone(0), table._zone(1))
+    return table, bloom, zone
 
 
 def count(tables: Sequence[Table], ranges=None, prefixes=None, stream=None):
@@ -1102,12 +1089,7 @@ def compact_live(tables: Sequence[Table], m: int = 1024, stream=None):
     arr, dev = _table_list(tables)
     th, fh = ctypes.c_void_p(), ctypes.c_void_p()
     _raise(_L().cb_tables_compact_live(arr, len(tables), int(m), _stream(stream), ctypes.byref(th), ctypes.byref(fh)))
-    table = Table._adopt(th.value, dev)
-    bloom = BloomFilter(0, device=dev, _handle=fh.value)
-    zone = ZoneMap()
-    if table.nlines:
-        zone = ZoneMap(table._zone(0), table._zone(1))
-    return table, bloom, zone
+    return _adopt_compaction(th, fh, dev)
 
 
 def compact_lww(tables: Sequence[Table], m: int = 1024, drop_dead: bool = False, stream=None):
@@ -1128,12 +1110,7 @@ def compact_lww(tables: Sequence[Table], m: int = 1024, drop_dead: bool = False,
     th, fh = ctypes.c_void_p(), ctypes.c_void_p()
     _raise(_L().cb_tables_compact_lww(arr, len(tables), int(m), int(bool(drop_dead)), _stream(stream),
                                       ctypes.byref(th), ctypes.byref(fh)))
-    table = Table._adopt(th.value, dev)
-    bloom = BloomFilter(0, device=dev, _handle=fh.value)
-    zone = ZoneMap()
-    if table.nlines:
-        zone = ZoneMap(table._zone(0), table._zone(1))
-    return table, bloom, zone
+    return _adopt_compaction(th, fh, dev)
 
 
 def scan_lww(tables: Sequence[Table], ranges=None, prefixes=None, limit: int = 0, drop_dead: bool = False,

@@ -2,9 +2,10 @@
 // (capi_runtime.cpp: errors, the block pool, workspaces, staging;
 // capi_filter.cpp: filters, insert / probe, the codec's device halves;
 // capi_set.cpp: filter sets, zones, tiers, the exchange entries;
-// capi_table.cpp, capi_flush.cpp, capi_get.cpp, capi_merge.cpp: SSTable files,
-// SsTable::create, the read path, compaction and scans; those four share
-// capi_table.hpp besides): the handle structs, error reporting, device
+// capi_table.cpp, capi_flush.cpp, capi_get.cpp, capi_merge.cpp, capi_scan.cpp:
+// SSTable files, SsTable::create, the read path, the merge with compaction,
+// scans and counts; those five share capi_table.hpp besides, the last two
+// capi_merge.hpp): the handle structs, error reporting, device
 // buffers, the block pool, per-stream workspaces and the host frame around a
 // keyed launch.
 #pragma once

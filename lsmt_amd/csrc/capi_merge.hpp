@@ -1,0 +1,86 @@
+// capi_merge.hpp — what the two users of the device merge share
+// (capi_merge.cpp: the merge itself, the table-list checks and compaction;
+// capi_scan.cpp: scans, counts and the scan result). Included only by them.
+#pragma once
+#include "capi_table.hpp"
+#include "compact.hpp"
+
+namespace cbx {
+
+constexpr cb::MergeRule kNewest{cb::MergeOrder::newest, false};  // the plain entries' rule
+constexpr cb::MergeRule kLive{cb::MergeOrder::newest, true};     // the live-row entries'
+
+// ---- the table list every entry takes (capi_merge.cpp) ----
+
+// A non-empty list without a null table, all on one device (*dev).
+int check_table_list(const cb_table* const* tables, uint32_t nt, int* dev);
+
+// each(table, its place in the list) for the non-empty tables, newest first:
+// every table is finalised on the way, and one that is not well-formed refused.
+template <class Each>
+int for_live_tables(const cb_table* const* tables, uint32_t nt, Each each) {
+  for (uint32_t i = 0; i < nt; ++i) {
+    cb_table* ti = const_cast<cb_table*>(tables[i]);
+    if (int rc = finalize_table(ti)) return rc;
+    if (!ti->nlines) continue;
+    if (!ti->fast) return fail(CB_EINVAL, "an input table is not well-formed");
+    each(ti, i);
+  }
+  return CB_OK;
+}
+
+// ---- the merge (capi_merge.cpp) ----
+
+// The newest-wins merge that cb_tables_compact and cb_tables_scan run over
+// their sources (compact.hpp): the lines' keys gathered into one batch, the
+// stable key sort, the select of each key's newest decodable line and the
+// scanned tile sums of the survivors. Its scratch is one pool block.
+struct Merge {
+  uint64_t n = 0, kbound = 0, tiles = 0;  // lines, a bound on their keys' bytes, select tiles
+  SortPlan plan{};
+  cb::CompactSrc* dsrc = nullptr;  // room for the caller's sources (nsrc_cap of them)
+  uint64_t *klen = nullptr, *ko = nullptr, *scan = nullptr;
+  uint8_t* kb = nullptr;
+  cb::CompactSide* side = nullptr;
+  cb::SortKey* order = nullptr;
+  uint8_t* sort = nullptr;
+  uint64_t *slen = nullptr, *tcnt = nullptr, *tbytes = nullptr, *tkeys = nullptr, *tot = nullptr;
+  uint64_t* ts = nullptr;  // the lines' timestamps: an LWW merge's only
+  cb::CreateResult* dr = nullptr;
+};
+int merge_alloc(uint32_t nsrc_cap, uint64_t n, uint64_t kbound, cb::MergeOrder order, TempBlock& tmp, Merge* m);
+// The merge of sources dsrc[0..nsrc) (device, m.n lines in all) on s, up to
+// and including the select (nothing is waited for): the sorted order and, per
+// sorted record, whether it survives (slen) with the tiles' sums. The rule
+// (compact.hpp) picks the select: newest enqueues k_compact_select, lww the
+// lines' timestamps and the two launches of the LWW select (m was allocated
+// for the same order); drop_dead: either keeps no tombstone (liverow.hpp).
+int enqueue_merge_select(const Merge& m, const cb::CompactSrc* dsrc, uint32_t nsrc, cb::MergeRule rule, hipStream_t s);
+// The rest of the merge for a caller that writes the survivors out: the scans
+// of the tile sums and the survivors' totals h = {lines, file bytes, key
+// bytes}, read back (they size the caller's output), the stream waited for,
+// and checked against the inputs' bounds before anything is sized from them.
+// (A count stops at the select: it places no survivor.)
+int enqueue_merge(const Merge& m, const cb::CompactSrc* dsrc, uint32_t nsrc, cb::MergeRule rule, hipStream_t s,
+                  uint64_t (&h)[3]);
+
+// ---- host values on their way into a call's scratch block ----
+
+// The parts carved from c before seal() are staged: filled at their carved
+// offsets in a zeroed host copy, they go up in one copy to the front of the
+// block allocated from c. What is carved after seal() is the device's alone.
+// The host copy is pageable: it must outlive the copy (a wait on the stream).
+struct Staging {
+  cb::Carver c;
+  std::vector<uint8_t> host;
+  void seal() { host.assign(c.total(), 0); }
+  uint8_t* at(size_t off) { return &host[off]; }
+  void put(size_t off, const void* p, size_t bytes) {
+    if (bytes) std::memcpy(&host[off], p, bytes);
+  }
+  hipError_t upload(const TempBlock& b, hipStream_t s) const {
+    return hipMemcpyAsync(b.p, host.data(), host.size(), hipMemcpyHostToDevice, s);
+  }
+};
+
+}  // namespace cbx

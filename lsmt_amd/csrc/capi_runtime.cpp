@@ -3,8 +3,9 @@
 // per-stream workspaces and the stream registry, host buffer staging and the
 // end of a keyed call, and the library / stream / pinned-memory entry points.
 // Filters are in capi_filter.cpp, filter sets in capi_set.cpp, the SSTable
-// entry points in capi_table.cpp, capi_flush.cpp, capi_get.cpp and
-// capi_merge.cpp; what they all share is in capi_internal.hpp.
+// entry points in capi_table.cpp, capi_flush.cpp, capi_get.cpp,
+// capi_merge.cpp and capi_scan.cpp; what they all share is in
+// capi_internal.hpp.
 #include "capi_internal.hpp"
 
 namespace cbx {

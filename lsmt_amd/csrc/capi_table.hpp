@@ -1,7 +1,8 @@
-// capi_table.hpp — what the SSTable entries' four translation units share
+// capi_table.hpp — what the SSTable entries' five translation units share
 // (capi_table.cpp: the handle, its index and a file that already exists;
 // capi_flush.cpp: SsTable::create; capi_get.cpp: the read path;
-// capi_merge.cpp: compaction and scans). Included only by them.
+// capi_merge.cpp: the merge and compaction; capi_scan.cpp: scans and counts;
+// the last two share capi_merge.hpp besides). Included only by them.
 #pragma once
 #include "capi_internal.hpp"
 #include "tablehost.hpp"

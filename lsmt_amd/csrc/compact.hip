@@ -23,8 +23,9 @@
 //       it once), then the tile sums. Launched for LWW merges only.
 //   k_compact_format — one block per tile: the survivors' offsets from the
 //       scanned tile sums and a block scan, then the block copies the tile's
-//       bytes together, aligned dwords of the output assembled from the
-//       source lines (a line is `key \t text` in its input file already, so
+//       bytes together (copy_tile_bytes, compact.hpp: the scan's emit copies
+//       its keys the same way), aligned dwords of the output assembled from
+//       the source lines (a line is `key \t text` in its input file already, so
 //       only the '\n' is new). Each survivor also writes its entry of the
 //       line index (LineRec with vdl carried over, pfx, the fence levels,
 //       llen: the file is never re-read) and packs its key for the Bloom
@@ -86,6 +87,20 @@ __device__ __forceinline__ bool same_key(const SortKey& a, const SortKey& b, con
   return bytes_cmp(kb + ko[a.idx] + 16, a.len - 16, kb + ko[b.idx] + 16, b.len - 16) == 0;
 }
 
+// A tile's three sums from its lanes' line lengths (0: not a survivor) and key
+// lengths: the survivors, their line bytes and their key bytes. Contains
+// barriers: every lane of the block calls it.
+__device__ __forceinline__ void put_tile_sums(uint64_t len, uint64_t kl, uint64_t* __restrict__ tcnt,
+                                              uint64_t* __restrict__ tbytes, uint64_t* __restrict__ tkeys) {
+  uint64_t tc, tl, tk;
+  (void)block_scan_sum2<(int)kNT>(len ? 1 : 0, len, kl, &tc, &tl, &tk);
+  if (threadIdx.x == 0) {
+    tcnt[blockIdx.x] = tc;
+    tbytes[blockIdx.x] = tl;
+    tkeys[blockIdx.x] = tk;
+  }
+}
+
 template <bool DropDead>
 __global__ __launch_bounds__(kNT) void k_compact_select(const SortKey* __restrict__ order,
                                                         const CompactSide* __restrict__ side,
@@ -117,13 +132,7 @@ __global__ __launch_bounds__(kNT) void k_compact_select(const SortKey* __restric
     }
     slen[p] = len;
   }
-  uint64_t tc, tl, tk;
-  (void)block_scan_sum2<(int)kNT>(len ? 1 : 0, len, kl, &tc, &tl, &tk);
-  if (threadIdx.x == 0) {
-    tcnt[blockIdx.x] = tc;
-    tbytes[blockIdx.x] = tl;
-    tkeys[blockIdx.x] = tk;
-  }
+  put_tile_sums(len, kl, tcnt, tbytes, tkeys);
 }
 
 __global__ __launch_bounds__(kNT) void k_compact_ts(const CompactSide* __restrict__ side, uint64_t n,
@@ -193,13 +202,7 @@ __global__ __launch_bounds__(kNT) void k_compact_lww_tiles(const SortKey* __rest
   const uint64_t p = (uint64_t)blockIdx.x * kNT + threadIdx.x;
   const uint64_t len = p < n ? slen[p] : 0;
   const uint64_t kl = len ? side[order[p].idx].klen : 0;
-  uint64_t tc, tl, tk;
-  (void)block_scan_sum2<(int)kNT>(len ? 1 : 0, len, kl, &tc, &tl, &tk);
-  if (threadIdx.x == 0) {
-    tcnt[blockIdx.x] = tc;
-    tbytes[blockIdx.x] = tl;
-    tkeys[blockIdx.x] = tk;
-  }
+  put_tile_sums(len, kl, tcnt, tbytes, tkeys);
 }
 
 __global__ __launch_bounds__(kNT) void k_compact_format(const SortKey* __restrict__ order,
@@ -242,33 +245,11 @@ __global__ __launch_bounds__(kNT) void k_compact_format(const SortKey* __restric
   }
   if (threadIdx.x == 0) s_off[tc] = tl;
   __syncthreads();
-  const uint32_t nsv = (uint32_t)tc;
-  // byte j of the tile: survivor i = the last with s_off[i] <= j
-  auto line_of = [&](uint64_t j) { return last_le(nsv, j, [&](uint32_t i) { return s_off[i]; }); };
-  auto byte_at = [&](uint32_t i, uint64_t j) -> uint32_t {
+  // the tile's lines: a survivor's `key \t text` from its file, then the '\n'
+  copy_tile_bytes(out + tbytes[blockIdx.x], tl, (uint32_t)tc, s_off, [&](uint32_t i, uint64_t j) -> uint32_t {
     const uint64_t b = j - s_off[i];
     return b < s_ll[i] ? s_src[i][b] : (uint32_t)'\n';
-  };
-  // out[base .. base + tl): bytes up to the first 4-aligned address, then
-  // aligned dwords, then the tail
-  uint8_t* g = out + tbytes[blockIdx.x];
-  const uint64_t mis = (4 - ((uintptr_t)g & 3)) & 3;
-  const uint64_t head = mis < tl ? mis : tl;
-  if (threadIdx.x < head) g[threadIdx.x] = (uint8_t)byte_at(line_of(threadIdx.x), threadIdx.x);
-  const uint64_t body = (tl - head) / 4;
-  uint32_t* gw = reinterpret_cast<uint32_t*>(g + head);
-  for (uint64_t w = threadIdx.x; w < body; w += kNT) {
-    const uint64_t j0 = head + 4 * w;
-    uint32_t i = line_of(j0), v = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < 4; ++k) {
-      while (j0 + k >= s_off[i + 1]) ++i;  // (j0 + k < tl = s_off[nsv]: stops at a survivor)
-      v |= byte_at(i, j0 + k) << (8 * k);
-    }
-    gw[w] = v;
-  }
-  const uint64_t tail0 = head + 4 * body;
-  if (tail0 + threadIdx.x < tl) g[tail0 + threadIdx.x] = (uint8_t)byte_at(line_of(tail0 + threadIdx.x), tail0 + threadIdx.x);
+  });
 }
 
 }  // namespace

@@ -47,6 +47,40 @@ __device__ __forceinline__ uint32_t src_of(const CompactSrc* __restrict__ src, u
   return last_le(nsrc, g, [&](uint32_t i) { return src[i].base; });
 }
 
+constexpr uint32_t kCompactTile = 256;  // records per select / format block
+
+// The bytes of one tile of survivors written by its whole block (kCompactTile
+// lanes, after the barrier behind s_off): o[0 .. tl) where survivor i of nsv
+// owns bytes s_off[i] .. s_off[i + 1) (s_off[nsv] = tl; a survivor may own
+// none) and byte_at(i, j) is byte j of the tile, which survivor i owns. Bytes
+// up to the first 4-aligned address, then aligned dwords assembled across the
+// survivors, then the tail. (threadIdx.x is written out at each use: held in
+// a local, k_compact_format's allocation grew by two VGPRs.)
+template <class ByteAt>
+__device__ __forceinline__ void copy_tile_bytes(uint8_t* o, uint64_t tl, uint32_t nsv, const uint64_t* s_off,
+                                                ByteAt byte_at) {
+  // byte j's survivor: the last with s_off[i] <= j (of equal offsets the last
+  // is the one that owns a byte)
+  auto owner = [&](uint64_t j) { return last_le(nsv, j, [&](uint32_t i) { return s_off[i]; }); };
+  const uint64_t mis = (4 - ((uintptr_t)o & 3)) & 3;
+  const uint64_t head = mis < tl ? mis : tl;
+  if (threadIdx.x < head) o[threadIdx.x] = (uint8_t)byte_at(owner(threadIdx.x), threadIdx.x);
+  const uint64_t body = (tl - head) / 4;
+  uint32_t* ow = reinterpret_cast<uint32_t*>(o + head);
+  for (uint64_t w = threadIdx.x; w < body; w += kCompactTile) {
+    const uint64_t j0 = head + 4 * w;
+    uint32_t i = owner(j0), x = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < 4; ++k) {
+      while (j0 + k >= s_off[i + 1]) ++i;  // (j0 + k < tl = s_off[nsv]: stops at a survivor)
+      x |= byte_at(i, j0 + k) << (8 * k);
+    }
+    ow[w] = x;
+  }
+  const uint64_t tail0 = head + 4 * body;
+  if (tail0 + threadIdx.x < tl) o[tail0 + threadIdx.x] = (uint8_t)byte_at(owner(tail0 + threadIdx.x), tail0 + threadIdx.x);
+}
+
 // What the later passes need of input line g once the sort has moved its
 // record: where `key \t text` starts, its length (the line without '\n'), the
 // key's length and the value's decoded length.
@@ -55,7 +89,6 @@ struct CompactSide {
   uint32_t llen, klen, vdl, pad;
 };
 
-constexpr uint32_t kCompactTile = 256;  // records per select / format block
 inline uint64_t compact_tiles(uint64_t n) { return n ? (n + kCompactTile - 1) / kCompactTile : 1; }
 
 // klen[g] = the key length of global line g (the scan of these is ko).

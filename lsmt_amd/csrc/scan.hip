@@ -16,7 +16,8 @@
 //       with its table's place in the caller's list and its range.
 //   k_scan_emit — one block per tile of sorted records, as k_compact_format:
 //       the survivors' ranks and key offsets from the scanned tile sums and a
-//       block scan, the tile's key bytes assembled into aligned dwords, and
+//       block scan, the tile's key bytes assembled into aligned dwords
+//       (compaction's copier, copy_tile_bytes of compact.hpp), and
 //       per survivor its key offset, source and value span. A tile's
 //       survivors lie in at most two of the decode's tiles, so the block adds
 //       two partial sums of their decoded lengths. For a scan of many ranges
@@ -26,7 +27,8 @@
 //   k_scan_count — cb_tables_count's tail, in place of the emit and all after
 //       it: one block per tile of sorted records, the survivors and the live
 //       ones (liverow.hpp) summed per run of equal ranges and added to the
-//       ranges' counters. No key is copied and no value read.
+//       ranges' counters (count_runs, the tail it shares with
+//       k_scan_count_where). No key is copied and no value read.
 //   k_scan_ts — cb_scan_ts: one lane per entry of a finished result, its
 //       timestamp from its decoded value's first 8 bytes (rowts.hpp).
 //   k_scan_count_where — cb_tables_count_where's tail, k_scan_count's shape
@@ -232,31 +234,10 @@ __global__ __launch_bounds__(kNT) void k_scan_emit(const SortKey* __restrict__ o
   __syncthreads();
   const uint32_t nsv = r0 >= count ? 0u : (uint32_t)(count - r0 < tc ? count - r0 : tc);  // survivors under the limit
   if (!nsv) return;  // (uniform)
+  // the tile's keys back to back (an empty key owns no byte)
   const uint64_t tl = s_off[nsv];
-  // byte j of the tile's keys: survivor i = the last with s_off[i] <= j (an
-  // empty key owns no byte: the last of equal offsets is the one that does)
-  auto key_of = [&](uint64_t j) { return last_le(nsv, j, [&](uint32_t i) { return s_off[i]; }); };
-  auto byte_at = [&](uint32_t i, uint64_t j) -> uint32_t { return s_src[i][j - s_off[i]]; };
-  // keys[base .. base + tl): bytes up to the first 4-aligned address, then
-  // aligned dwords, then the tail
-  uint8_t* o = keys + tkeys[blockIdx.x];
-  const uint64_t mis = (4 - ((uintptr_t)o & 3)) & 3;
-  const uint64_t head = mis < tl ? mis : tl;
-  if (threadIdx.x < head) o[threadIdx.x] = (uint8_t)byte_at(key_of(threadIdx.x), threadIdx.x);
-  const uint64_t body = (tl - head) / 4;
-  uint32_t* ow = reinterpret_cast<uint32_t*>(o + head);
-  for (uint64_t w = threadIdx.x; w < body; w += kNT) {
-    const uint64_t j0 = head + 4 * w;
-    uint32_t i = key_of(j0), x = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < 4; ++k) {
-      while (j0 + k >= s_off[i + 1]) ++i;  // (j0 + k < tl = s_off[nsv]: stops at a survivor)
-      x |= byte_at(i, j0 + k) << (8 * k);
-    }
-    ow[w] = x;
-  }
-  const uint64_t tail0 = head + 4 * body;
-  if (tail0 + threadIdx.x < tl) o[tail0 + threadIdx.x] = (uint8_t)byte_at(key_of(tail0 + threadIdx.x), tail0 + threadIdx.x);
+  copy_tile_bytes(keys + tkeys[blockIdx.x], tl, nsv, s_off,
+                  [&](uint32_t i, uint64_t j) -> uint32_t { return s_src[i][j - s_off[i]]; });
 }
 
 // One lane per r in [0, nr]: the first entry of the non-decreasing rid[0..count)
@@ -274,31 +255,21 @@ __global__ __launch_bounds__(kNT) void k_scan_range_off(const uint32_t* __restri
   range_off[r] = lo;
 }
 
-// One block per tile of sorted records, after the plain select. Every record,
-// survivor or not, has its source's range, and the ranges do not decrease
-// along the sorted order, so a tile is a few runs of equal ranges. One block
-// scan of two packed flags (survivor in the low word, survivor and not dead
-// in the high one: neither passes 256), then each lane that ends a run adds
-// the run's two sums to its range's counters: as many pairs of atomics as the
-// tile holds ranges with an entry.
-__global__ __launch_bounds__(kNT) void k_scan_count(const SortKey* __restrict__ order,
-                                                    const CompactSide* __restrict__ side,
-                                                    const uint64_t* __restrict__ slen,
-                                                    const CompactSrc* __restrict__ src,
-                                                    const uint32_t* __restrict__ src_rng, uint32_t nsrc, uint64_t n,
-                                                    uint32_t nr, uint64_t* __restrict__ cnt) {
-  constexpr uint32_t kPast = 0xFFFFFFFFu;  // the range of a lane past the last record (nr - 1 is below it)
+constexpr uint32_t kPast = 0xFFFFFFFFu;  // the range of a lane past the last record (nr - 1 is below it)
+
+// The tail of both counting kernels, called by every lane of the block with
+// its record's range (kPast: no record) and its flags, Fields of them packed
+// Field bits apart (none passes 256). One block scan of the packed word, then
+// each lane that ends a run of equal ranges adds the run's sums to its
+// range's counters cnt[Fields rid ..]: as many atomics as the tile holds
+// ranges with an entry, times the fields that are not zero.
+template <uint32_t Field, uint32_t Fields>
+__device__ __forceinline__ void count_runs(uint64_t p, uint64_t n, uint32_t rid, uint64_t v, uint32_t nr,
+                                           uint64_t* __restrict__ cnt) {
+  static_assert(Field >= 9 && Field * Fields <= 64, "a tile's sums fit their fields");
   __shared__ uint32_t s_rid[kNT + 1];
   __shared__ uint64_t s_inc[kNT];  // the inclusive scan of the packed flags
   const uint32_t t = threadIdx.x;
-  const uint64_t p = (uint64_t)blockIdx.x * kNT + t;
-  uint32_t rid = kPast;
-  uint64_t v = 0;
-  if (p < n) {
-    const uint32_t g = order[p].idx;
-    rid = nr > 1 ? src_rng[src_of(src, nsrc, g)] : 0;  // (uniform)
-    if (slen[p]) v = value_dead(side[g].vdl) ? 1ull : 1ull | 1ull << 32;
-  }
   uint64_t total;
   const uint64_t inc = block_scan<(int)kNT>(v, &total) + v;
   s_rid[t] = rid;
@@ -314,9 +285,34 @@ __global__ __launch_bounds__(kNT) void k_scan_count(const SortKey* __restrict__ 
     else hi = mid;
   }
   const uint64_t sum = inc - (lo ? s_inc[lo - 1] : 0);
-  const unsigned long long entries = sum & 0xFFFFFFFFull, live = sum >> 32;
-  if (entries) atomicAdd((unsigned long long*)(cnt + 2ull * rid), entries);
-  if (live) atomicAdd((unsigned long long*)(cnt + 2ull * rid + 1), live);
+#pragma unroll
+  for (uint32_t k = 0; k < Fields; ++k) {
+    uint64_t f = sum >> k * Field;
+    if (k + 1 < Fields) f &= (1ull << Field) - 1;
+    if (f) atomicAdd((unsigned long long*)(cnt + (uint64_t)Fields * rid + k), (unsigned long long)f);
+  }
+}
+
+// One block per tile of sorted records, after the plain select. Every record,
+// survivor or not, has its source's range, and the ranges do not decrease
+// along the sorted order, so a tile is a few runs of equal ranges. Two flags
+// per lane (survivor in the low word, survivor and not dead in the high one)
+// summed per run by count_runs.
+__global__ __launch_bounds__(kNT) void k_scan_count(const SortKey* __restrict__ order,
+                                                    const CompactSide* __restrict__ side,
+                                                    const uint64_t* __restrict__ slen,
+                                                    const CompactSrc* __restrict__ src,
+                                                    const uint32_t* __restrict__ src_rng, uint32_t nsrc, uint64_t n,
+                                                    uint32_t nr, uint64_t* __restrict__ cnt) {
+  const uint64_t p = (uint64_t)blockIdx.x * kNT + threadIdx.x;
+  uint32_t rid = kPast;
+  uint64_t v = 0;
+  if (p < n) {
+    const uint32_t g = order[p].idx;
+    rid = nr > 1 ? src_rng[src_of(src, nsrc, g)] : 0;  // (uniform)
+    if (slen[p]) v = value_dead(side[g].vdl) ? 1ull : 1ull | 1ull << 32;
+  }
+  count_runs<32, 2>(p, n, rid, v, nr, cnt);
 }
 
 __global__ __launch_bounds__(kNT) void k_scan_ts(const uint64_t* __restrict__ val_off,
@@ -361,12 +357,8 @@ __global__ __launch_bounds__(kNT) void k_scan_count_where(const SortKey* __restr
                                                           uint64_t n, uint32_t nr, const WherePred* __restrict__ w,
                                                           const uint32_t* __restrict__ skip,
                                                           uint64_t* __restrict__ cnt) {
-  constexpr uint32_t kPast = 0xFFFFFFFFu;
   constexpr uint32_t kField = 21;
-  __shared__ uint32_t s_rid[kNT + 1];
-  __shared__ uint64_t s_inc[kNT];
-  const uint32_t t = threadIdx.x;
-  const uint64_t p = (uint64_t)blockIdx.x * kNT + t;
+  const uint64_t p = (uint64_t)blockIdx.x * kNT + threadIdx.x;
   uint32_t rid = kPast;
   uint64_t v = 0;
   if (p < n) {
@@ -382,25 +374,7 @@ __global__ __launch_bounds__(kNT) void k_scan_count_where(const SortKey* __restr
       }
     }
   }
-  uint64_t total;
-  const uint64_t inc = block_scan<(int)kNT>(v, &total) + v;
-  s_rid[t] = rid;
-  s_inc[t] = inc;
-  if (t == 0) s_rid[kNT] = kPast;
-  __syncthreads();
-  if (p >= n || s_rid[t + 1] == rid || rid >= nr) return;  // not the end of a run
-  uint32_t lo = 0, hi = t;  // s_rid[i] < rid for i < lo, s_rid[hi] == rid
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (s_rid[mid] < rid) lo = mid + 1;
-    else hi = mid;
-  }
-  const uint64_t sum = inc - (lo ? s_inc[lo - 1] : 0);
-  constexpr uint64_t kMask = (1ull << kField) - 1;
-  const unsigned long long entries = sum & kMask, live = sum >> kField & kMask, matched = sum >> 2 * kField;
-  if (entries) atomicAdd((unsigned long long*)(cnt + 3ull * rid), entries);
-  if (live) atomicAdd((unsigned long long*)(cnt + 3ull * rid + 1), live);
-  if (matched) atomicAdd((unsigned long long*)(cnt + 3ull * rid + 2), matched);
+  count_runs<kField, 3>(p, n, rid, v, nr, cnt);
 }
 
 __global__ __launch_bounds__(kNT) void k_scan_match(const uint64_t* __restrict__ key_off,

@@ -14,48 +14,17 @@ key as long as the table count across 256-record tiles and the sort's
 4096-record tiles, line totals around the tile sizes, keys around the 16-byte
 sort record, values around the base64 padding and the format pass's stages.
 """
-import base64
 
 import numpy as np
 import pytest
 
+from merge_help import absent_keys, b64, BAD, file_keys, hex_keys, named, ragged, raw_file, TILE
 from oracle import oracle
 
 pytestmark = pytest.mark.gpu
 
 CB_EINVAL = -1
-TILE = 256        # compact.hpp kCompactTile: records per select / format block
 SORT_TILE = 4096  # sort.hip kTile: records per block sort
-
-
-def ragged(items):
-    offs = np.zeros(len(items) + 1, np.uint64)
-    np.cumsum([len(x) for x in items], out=offs[1:])
-    data = np.frombuffer(b"".join(items), np.uint8).copy() if offs[-1] else np.zeros(1, np.uint8)
-    return data, offs
-
-
-def b64(v: bytes) -> bytes:
-    return base64.b64encode(v)
-
-
-def raw_file(lines, final_newline=True) -> bytes:
-    """A hand-written data file: lines = [(key, value text)] in file order."""
-    body = b"\n".join(k + b"\t" + t for k, t in lines)
-    return body + (b"\n" if final_newline and lines else b"")
-
-
-def file_keys(data: bytes):
-    """The keys of a file's lines, as SsTable::get splits it (src/sstable.rs:142-146)."""
-    return [ln.split(b"\t", 1)[0] for ln in data.split(b"\n") if ln]
-
-
-def absent_keys(keys, rng, n=64):
-    have = set(keys)
-    out = [k + b"!" for k in keys[:n]] + [k[:-1] for k in keys[:n] if k] + [b"", b"\xff" * 9]
-    out += [rng.integers(0, 256, int(rng.integers(1, 24)), dtype=np.uint8).tobytes().replace(b"\n", b"n").replace(b"\t", b"t")
-            for _ in range(n)]
-    return [k for k in dict.fromkeys(out) if k not in have]
 
 
 def expected(files, m):
@@ -117,10 +86,6 @@ def check(gpu, files, m=1024, tables=None, seed=0):
     return merged, bloom, z, want
 
 
-def named(t, k):
-    return b"t%d:" % t + k
-
-
 def overlap_files(nt, pool, rng, lo=1, hi=256):
     """nt tables of lo..hi lines drawn from pool; each table's values name the table."""
     files = []
@@ -129,11 +94,6 @@ def overlap_files(nt, pool, rng, lo=1, hi=256):
         ks = [pool[i] for i in rng.choice(len(pool), n, replace=False)]
         files.append(oracle.sstable_create([(k, named(t, k)) for k in ks]))
     return files
-
-
-def hex_keys(rng, n, kl=16):
-    h = rng.integers(0, 256, (n, kl // 2), dtype=np.uint8).tobytes().hex().encode()
-    return list(dict.fromkeys(h[i * kl:(i + 1) * kl] for i in range(n)))
 
 
 # ---- identity, one table, tiny tables ------------------------------------------------
@@ -231,6 +191,20 @@ def test_line_totals_at_tile_sizes(gpu, total):
     f1 = oracle.sstable_create([(k, named(1, k)) for k in older])
     assert len(file_keys(f0)) + len(file_keys(f1)) == total
     check(gpu, [f0, f1], seed=total)
+
+
+@pytest.mark.parametrize("start", [0, 1, 2, 3])
+def test_a_three_byte_tile_at_every_output_alignment(gpu, start):
+    """One table of 600 lines. The second format tile (records 256 to 511)
+    holds one survivor, the 3-byte line `b TAB NL` among 255 lines that do not
+    decode, and begins `start` bytes past a dword of the merged file: the tile
+    is all head, or all tail, or both, and has no whole dword."""
+    lines = [(b"a%03d" % i + b"x" * (start if i == 7 else 0), b64(b"v")) for i in range(TILE)]
+    lines += [(b"b", b"")] + [(b"b%03d" % i, BAD) for i in range(TILE - 1)]
+    lines += [(b"c%03d" % i, b64(b"w%d" % i)) for i in range(88)]
+    assert len(lines) == 600 and lines == sorted(lines) and lines[TILE][0] == b"b"
+    merged, _, _, want = check(gpu, [raw_file(lines)], seed=start)
+    assert want.index(b"\nb\t\n") + 1 == 10 * TILE + start and merged.nlines == TILE + 1 + 88
 
 
 def test_70001_lines_over_five_tables(gpu):

@@ -30,59 +30,15 @@ import numpy as np
 import pytest
 
 from liverow_ref import is_dead
+from merge_help import b64, BAD, file_keys, hex_keys, open_tables, oracle_prefix_end, ragged, raw_file, row, TILE, tomb
 from oracle import oracle
 
 pytestmark = pytest.mark.gpu
 
 CB_EINVAL = -1
-TILE = 256  # compact.hpp kCompactTile = scan.hip kNT
 
 
-# ---- helpers (tests/test_scan_many_gpu.py's) --------------------------------------------
-
-def ragged(items):
-    offs = np.zeros(len(items) + 1, np.uint64)
-    np.cumsum([len(x) for x in items], out=offs[1:])
-    data = np.frombuffer(b"".join(items), np.uint8).copy() if offs[-1] else np.zeros(1, np.uint8)
-    return data, offs
-
-
-def b64(v: bytes) -> bytes:
-    return base64.b64encode(v)
-
-
-def raw_file(lines, final_newline=True) -> bytes:
-    """A hand-written data file: lines = [(key, value text)] in file order."""
-    body = b"\n".join(k + b"\t" + t for k, t in lines)
-    return body + (b"\n" if final_newline and lines else b"")
-
-
-def file_keys(data: bytes):
-    return [ln.split(b"\t", 1)[0] for ln in data.split(b"\n") if ln]
-
-
-def hex_keys(rng, n, kl=16):
-    h = rng.integers(0, 256, (n, kl // 2), dtype=np.uint8).tobytes().hex().encode()
-    return list(dict.fromkeys(h[i * kl:(i + 1) * kl] for i in range(n)))
-
-
-def oracle_prefix_end(p: bytes):
-    q = p.rstrip(b"\xff")
-    return q[:-1] + bytes([q[-1] + 1]) if q else None
-
-
-def tomb(ts: int) -> bytes:
-    """exec_delete's value text: the 8-byte timestamp, no payload (src/query.rs:240-261)."""
-    return b64(ts.to_bytes(8, "big"))
-
-
-def row(ts: int, payload: bytes) -> bytes:
-    """A live row's value text: timestamp, then the payload."""
-    return b64(ts.to_bytes(8, "big") + payload)
-
-
-BAD = b"QQ="  # a text STANDARD.decode rejects
-
+# ---- the reference and the checks (shared helpers: tests/merge_help.py) ----
 
 class Ref:
     """The oracle's answer for every key of `files` (newest first), computed
@@ -126,10 +82,6 @@ def assert_result(r, want, what="", truncated=False):
     assert vb.tobytes() == b"".join(v for _, v, _ in want), f"{what}: values differ"
     assert r.which().tolist() == [w for _, _, w in want], f"{what}: sources differ"
     assert (r.key_bytes, r.val_bytes) == (int(eko[-1]), int(evo[-1])), what
-
-
-def open_tables(gpu, files):
-    return [gpu.Table(f) for f in files]
 
 
 def check_ranges(gpu, ref, tables, ranges=None, prefixes=None, stream=None):

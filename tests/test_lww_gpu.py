@@ -20,7 +20,6 @@ either side of it, runs longer than one and two tiles, two long runs back to
 back, keys that differ past their 16th byte only, and ranges that begin and
 end at a run.
 """
-import base64
 import ctypes
 
 import numpy as np
@@ -28,60 +27,16 @@ import pytest
 
 import lww_ref
 from liverow_ref import is_dead
+from merge_help import (ALL, b64, BAD, file_keys, hex_keys, open_tables, oracle_prefix_end, ragged,
+                        raw_file, row, table_lines, TILE, tomb)
 from oracle import oracle
 
 pytestmark = pytest.mark.gpu
 
 CB_EINVAL = -1
-TILE = 256  # compact.hpp kCompactTile
 
 
-# ---- helpers (tests/test_live_gpu.py's) -------------------------------------------------
-
-def ragged(items):
-    offs = np.zeros(len(items) + 1, np.uint64)
-    np.cumsum([len(x) for x in items], out=offs[1:])
-    data = np.frombuffer(b"".join(items), np.uint8).copy() if offs[-1] else np.zeros(1, np.uint8)
-    return data, offs
-
-
-def b64(v: bytes) -> bytes:
-    return base64.b64encode(v)
-
-
-def raw_file(lines, final_newline=True) -> bytes:
-    """A hand-written data file: lines = [(key, value text)] in file order."""
-    body = b"\n".join(k + b"\t" + t for k, t in lines)
-    return body + (b"\n" if final_newline and lines else b"")
-
-
-def file_keys(data: bytes):
-    return [ln.split(b"\t", 1)[0] for ln in data.split(b"\n") if ln]
-
-
-def hex_keys(rng, n, kl=16):
-    h = rng.integers(0, 256, (n, kl // 2), dtype=np.uint8).tobytes().hex().encode()
-    return list(dict.fromkeys(h[i * kl:(i + 1) * kl] for i in range(n)))
-
-
-def oracle_prefix_end(p: bytes):
-    q = p.rstrip(b"\xff")
-    return q[:-1] + bytes([q[-1] + 1]) if q else None
-
-
-def tomb(ts: int) -> bytes:
-    """exec_delete's value text: the 8-byte timestamp, no payload (src/query.rs:240-261)."""
-    return b64(ts.to_bytes(8, "big"))
-
-
-def row(ts: int, payload: bytes) -> bytes:
-    """A live row's value text: timestamp, then the payload."""
-    return b64(ts.to_bytes(8, "big") + payload)
-
-
-BAD = b"QQ="  # a text STANDARD.decode rejects
-ALL = [(b"", None)]  # everything, as one unbounded range
-
+# ---- the reference and the checks (shared helpers: tests/merge_help.py) ----
 
 class Ref:
     """Every table's own answers from the oracle (table r alone is replica r),
@@ -115,10 +70,6 @@ class Ref:
         return [x for p in parts for x in p], off
 
 
-def open_tables(gpu, files):
-    return [gpu.Table(f) for f in files]
-
-
 def assert_result(r, want, what="", truncated=False):
     """r holds exactly the entries `want` = [(key, value, which, ts)]."""
     assert r.count == len(want), f"{what}: {r.count} entries against {len(want)}"
@@ -133,14 +84,6 @@ def assert_result(r, want, what="", truncated=False):
     ts = r.ts()
     assert ts.dtype == np.uint64 and ts.tolist() == [x[3] for x in want], f"{what}: timestamps differ"
     assert (r.key_bytes, r.val_bytes) == (int(eko[-1]), int(evo[-1])), what
-
-
-def table_lines(gpu, t):
-    """cb_table_lines: (start, key_len, line_len) of every line."""
-    n = t.nlines
-    start, kl, ll = np.zeros(max(n, 1), np.uint64), np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32)
-    gpu._lib.check(gpu._lib.load().cb_table_lines(t._h, start.ctypes.data, kl.ctypes.data, ll.ctypes.data))
-    return start[:n].tolist(), kl[:n].tolist(), ll[:n].tolist()
 
 
 def expected_compaction(ref, drop, m):

@@ -18,50 +18,18 @@ runs of one key as long as the table count across a 256-record tile; totals
 of lines and survivors around the tile sizes; values around the base64
 padding and the decode's 16384-byte stage.
 """
-import base64
 import ctypes
 
 import numpy as np
 import pytest
 
+from merge_help import b64, file_keys, hex_keys, named, open_tables, oracle_prefix_end, ragged, raw_file, TILE
 from oracle import oracle
 
 pytestmark = pytest.mark.gpu
 
 CB_EINVAL = -1
-TILE = 256          # compact.hpp kCompactTile / sstable.hpp kDecodeTile
 DECODE_LDS = 16384  # b64decode.hip kDecodeLds
-
-
-def ragged(items):
-    offs = np.zeros(len(items) + 1, np.uint64)
-    np.cumsum([len(x) for x in items], out=offs[1:])
-    data = np.frombuffer(b"".join(items), np.uint8).copy() if offs[-1] else np.zeros(1, np.uint8)
-    return data, offs
-
-
-def b64(v: bytes) -> bytes:
-    return base64.b64encode(v)
-
-
-def raw_file(lines, final_newline=True) -> bytes:
-    """A hand-written data file: lines = [(key, value text)] in file order."""
-    body = b"\n".join(k + b"\t" + t for k, t in lines)
-    return body + (b"\n" if final_newline and lines else b"")
-
-
-def file_keys(data: bytes):
-    """The keys of a file's lines, as SsTable::get splits it (src/sstable.rs:142-146)."""
-    return [ln.split(b"\t", 1)[0] for ln in data.split(b"\n") if ln]
-
-
-def named(t, k):
-    return b"t%d:" % t + k
-
-
-def hex_keys(rng, n, kl=16):
-    h = rng.integers(0, 256, (n, kl // 2), dtype=np.uint8).tobytes().hex().encode()
-    return list(dict.fromkeys(h[i * kl:(i + 1) * kl] for i in range(n)))
 
 
 class Ref:
@@ -110,18 +78,6 @@ def check(gpu, ref, tables, lo=b"", hi=None, prefix=None, limit=0, stream=None):
     want, more = ref.expect(lo, hi, limit)
     assert_result(r, want, more, f"lo={lo[:24]!r} hi={None if hi is None else hi[:24]!r} limit={limit}")
     return r, want
-
-
-def oracle_prefix_end(p: bytes):
-    """The least byte string above every string that starts with p, worked out
-    here (not by the library): the first key k > p, in a brute-force sense,
-    that does not start with p is p's last non-0xFF byte incremented."""
-    q = p.rstrip(b"\xff")
-    return q[:-1] + bytes([q[-1] + 1]) if q else None
-
-
-def open_tables(gpu, files):
-    return [gpu.Table(f) for f in files]
 
 
 # ---- bounds -------------------------------------------------------------------------

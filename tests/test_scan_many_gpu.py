@@ -18,52 +18,20 @@ and most of them empty; k_scan_emit and k_scan_range_off at range boundaries
 on both sides of the 256-record tile edge, with empty ranges at the ends and
 in a row; the sort at 4096 and 4097 lines inside the ranges.
 """
-import base64
 import ctypes
 
 import numpy as np
 import pytest
 
+from merge_help import b64, BAD, file_keys, hex_keys, named, open_tables, oracle_prefix_end, ragged, raw_file, TILE
 from oracle import oracle
 
 pytestmark = pytest.mark.gpu
 
 CB_EINVAL = -1
-TILE = 256  # scan.hip kNT = compact.hpp kCompactTile
 
 
-# ---- helpers (tests/test_scan_gpu.py's) -----------------------------------------------
-
-def ragged(items):
-    offs = np.zeros(len(items) + 1, np.uint64)
-    np.cumsum([len(x) for x in items], out=offs[1:])
-    data = np.frombuffer(b"".join(items), np.uint8).copy() if offs[-1] else np.zeros(1, np.uint8)
-    return data, offs
-
-
-def b64(v: bytes) -> bytes:
-    return base64.b64encode(v)
-
-
-def raw_file(lines, final_newline=True) -> bytes:
-    """A hand-written data file: lines = [(key, value text)] in file order."""
-    body = b"\n".join(k + b"\t" + t for k, t in lines)
-    return body + (b"\n" if final_newline and lines else b"")
-
-
-def file_keys(data: bytes):
-    """The keys of a file's lines, as SsTable::get splits it (src/sstable.rs:142-146)."""
-    return [ln.split(b"\t", 1)[0] for ln in data.split(b"\n") if ln]
-
-
-def named(t, k):
-    return b"t%d:" % t + k
-
-
-def hex_keys(rng, n, kl=16):
-    h = rng.integers(0, 256, (n, kl // 2), dtype=np.uint8).tobytes().hex().encode()
-    return list(dict.fromkeys(h[i * kl:(i + 1) * kl] for i in range(n)))
-
+# ---- the reference and the checks (shared helpers: tests/merge_help.py) ----
 
 class Ref:
     """The oracle's answer for every key of `files` (newest first), computed
@@ -107,11 +75,6 @@ def assert_result(r, want, what=""):
     assert (r.key_bytes, r.val_bytes) == (int(eko[-1]), int(evo[-1])), what
 
 
-def oracle_prefix_end(p: bytes):
-    q = p.rstrip(b"\xff")
-    return q[:-1] + bytes([q[-1] + 1]) if q else None
-
-
 def brief(ranges):
     return [(lo[:12], None if hi is None else hi[:12]) for lo, hi in ranges[:8]]
 
@@ -128,10 +91,6 @@ def check_many(gpu, ref, tables, ranges=None, prefixes=None, stream=None):
     assert np.array_equal(r.range_off(), off), f"{what}: range offsets {r.range_off().tolist()} against {off.tolist()}"
     assert_result(r, want, what)
     return r, want, off
-
-
-def open_tables(gpu, files):
-    return [gpu.Table(f) for f in files]
 
 
 def ranges_from(bounds, last_unbounded=False):
@@ -320,6 +279,25 @@ def test_one_range_over_three_tiles_between_two_single_entries(gpu):
     tables = open_tables(gpu, files)
     r, want, off = check_many(gpu, ref, tables, prefixes=[b"n0:", b"n1:", b"n2:"])
     assert off.tolist() == [0, 1, 2 * TILE + 41, 2 * TILE + 42]
+
+
+@pytest.mark.parametrize("start", [0, 1, 2, 3])
+def test_a_tile_of_under_four_key_bytes_at_every_alignment(gpu, start):
+    """One table of 600 lines in two ranges. The second emit tile (records 256
+    to 511) holds one survivor, a key of 1 to 3 bytes among 255 lines that do
+    not decode, and its keys begin `start` bytes past a dword of the result's
+    keys: the tile is all head, or all tail, or both, and has no whole dword."""
+    short = b"b" * (1 + start % 3)
+    lines = [(b"a%03d" % i + b"x" * (start if i == 7 else 0), b64(b"v%d" % i)) for i in range(TILE)]
+    lines += [(short, b64(b"short"))] + [(b"b~%03d" % i, BAD) for i in range(TILE - 1)]
+    lines += [(b"c%03d" % i, b64(b"w%d" % i)) for i in range(88)]
+    assert len(lines) == 600 and lines == sorted(lines) and lines[TILE][0] == short
+    files = [raw_file(lines)]
+    ref = Ref(files)
+    r, want, off = check_many(gpu, ref, open_tables(gpu, files), ranges=[(b"", b"b~"), (b"b~", None)])
+    assert off.tolist() == [0, TILE + 1, TILE + 1 + 88]
+    ko = r.raw()[0]
+    assert want[TILE][0] == short and int(ko[TILE]) % 4 == start and int(ko[TILE + 1] - ko[TILE]) < 4
 
 
 # ---- touching ranges and runs of one key ------------------------------------------------

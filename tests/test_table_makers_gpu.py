@@ -17,8 +17,8 @@ sort one bin and so run its merge-sort fallback.
 import numpy as np
 import pytest
 
+from merge_help import absent_keys, ragged
 from oracle import oracle
-from test_compact_gpu import absent_keys, ragged
 
 pytestmark = pytest.mark.gpu
 

@@ -126,11 +126,37 @@ def test_the_rule_has_one_home():
             users.append(fn)
         assert not re.search(r"\b(where_json_conditions|where_key_conditions)\b", code), fn
         assert "'|'" not in code, fn  # no second split of a key into parts
-    assert users == ["capi_merge.cpp", "scan.hip"]
+    assert users == ["capi_scan.cpp", "scan.hip"]
     with open(os.path.join(CSRC, "scan.hip")) as fh:
         scan = fh.read()
     for kernel in ("k_scan_count_where", "k_scan_match", "k_scan_count"):
         assert re.search(r"__global__[^;{]*\b%s\s*\(" % kernel, scan), kernel
+
+
+def test_the_merge_kernels_repeated_steps_have_one_home():
+    """The steps that k_scan_count / k_scan_count_where, k_scan_emit /
+    k_compact_format and k_compact_select / k_compact_lww_tiles share are each
+    written once in csrc/, and both kernels of each pair go through that one body."""
+    code = {}
+    for fn in sorted(os.listdir(CSRC)):
+        if fn.endswith((".hip", ".hpp", ".cpp")):
+            with open(os.path.join(CSRC, fn)) as fh:
+                code[fn] = re.sub(r"//[^\n]*", "", fh.read())
+    homes = {"s_off[i + 1]) ++i": "compact.hpp",       # the dword-assembly walk of the tile copier
+             "s_rid[mid] < rid": "scan.hip",            # the search for a run's first lane
+             "tkeys[blockIdx.x] = tk": "compact.hip"}   # the three-sum tile write
+    for token, home in homes.items():
+        assert {fn: c.count(token) for fn, c in code.items() if token in c} == {home: 1}, token
+    scan, compact = code["scan.hip"], code["compact.hip"]
+    assert [len(re.findall(r"\bcopy_tile_bytes\s*\(", c)) for c in (scan, compact, code["compact.hpp"])] == [1, 1, 1]
+    assert len(re.findall(r"\bcount_runs\s*<[^>]*>\s*\(", scan)) == 2     # the two counting kernels
+    assert len(re.findall(r"\bput_tile_sums\s*\(", compact)) == 3          # its definition and the two selects
+    for kernel in ("k_scan_count", "k_scan_count_where", "k_scan_emit"):
+        assert re.search(r"__global__[^;{]*\b%s\s*\(" % kernel, scan), kernel
+    for kernel in ("k_compact_format", "k_compact_select", "k_compact_lww_tiles"):
+        assert re.search(r"__global__[^;{]*\b%s\s*\(" % kernel, compact), kernel
+    # the copier's header names nothing of the row rules
+    assert not re.search(r"liverow|rowts|rowjson|value_dead|row_matches|decoded_ts", code["compact.hpp"])
 
 
 # ---- argument errors --------------------------------------------------------------------

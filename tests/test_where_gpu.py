@@ -32,7 +32,8 @@ import pytest
 import lww_ref
 import rowjson_ref
 from liverow_ref import is_dead
-from test_live_gpu import BAD, TILE, Ref, b64, file_keys, open_tables, oracle_prefix_end, raw_file, row, tomb
+from merge_help import b64, BAD, file_keys, open_tables, oracle_prefix_end, raw_file, row, TILE, tomb
+from test_live_gpu import Ref
 from where_cases import CASES
 
 pytestmark = pytest.mark.gpu
