@@ -616,6 +616,94 @@ int cb_scan_match(const void* r, const uint32_t* skip /* one per range of r, nul
  * store merges over the tables' answer as it does for get. *out = 1 or 0. */
 int cb_row_matches(const uint8_t* key, uint64_t key_len, uint32_t skip, const uint8_t* value,
                    uint64_t value_len, const void* w /* cb_where */, int* out);
+/* ---- SELECT a, b: rows projected and re-encoded on the device ------------------
+ * The other half of the SQL read path. For SELECT a, b FROM t WHERE pk IN (...)
+ * the reference's exec_select_schema (src/query.rs:365-432) gets every key and,
+ * per row: split_ts (src/query.rs:21-27); a row without payload is deleted
+ * (src/query.rs:396-400); decode_row (src/schema.rs:42-44); the key's
+ * `|`-separated parts laid over the map as the key columns
+ * (src/query.rs:402-405); project_row with cast_simple (src/query.rs:641-662,
+ * 817-827); encode_row (src/schema.rs:37-39); and joins the rows into the
+ * response: a JSON array for a client (src/query.rs:411-431), `key\tts\tval`
+ * lines for a coordinator (src/cluster.rs:404-421 parses and folds them). The
+ * entries below write that response, byte for byte, from rows that are already
+ * in device memory. The rule's full text (column lookup, the integer cast, the
+ * escapes written) is lsmt_amd/csrc/rowselect.hpp's, over rowjson.hpp's
+ * grammar; like it, a restatement that was not run against the reference.
+ * A selection is nc <= 16 columns: column c's name cols[col_off[c] ..
+ * col_off[c+1]) (at most 4096 bytes together; empty names are legal), part[c]
+ * as in cb_where, cast[c] = 0 (none; Text, Varchar and Char too) or 1 (integer:
+ * a value str::parse::<i64> accepts becomes its i64::to_string, any other stays
+ * as it is). The names must ascend strictly, bytewise: that is the order a
+ * BTreeMap writes them in, so nothing is sorted per row.
+ * A row's column is its key part part[c] when 0 <= part[c] < nparts (the
+ * payload is not consulted), else the last pair of that name in the payload's
+ * map; a column without a value is left out, and a payload with an error
+ * anywhere is the empty map. The row's object is {"name":"value",...} in
+ * selection order, no spaces, strings escaped as serde_json writes them.
+ * flags[i]: CB_ROW_TEXT the row has text; CB_ROW_DEAD; CB_ROW_ABSENT (which[i]
+ * < 0); CB_ROW_BADJSON the payload is no valid map; CB_ROW_EXTRA a valid map
+ * holds a name that is not in the selection. Every live row's payload is
+ * parsed, so the last two are defined for every live row. SELECT * is exact
+ * without a wildcard: pass all of the schema's columns; a row without
+ * CB_ROW_EXTRA is then the reference's wildcard row, and the rows with it are
+ * done again on the host from cb_scan_values.
+ * CB_SELECT_JSON: a live row's text is its object, dead and absent rows have
+ * none; the response is [ + the texts joined by , + ] and [] without any.
+ * CB_SELECT_META: a live row's text is the key after skip, \t, ts in decimal,
+ * \t, the object; a dead row's is key \t ts \t alone; absent rows have none;
+ * the response is the texts joined by \n, no trailing newline, and no byte at
+ * all without any (the reference's Ok(None)).
+ * CB_EINVAL before any device work, *out = NULL: sel NULL; a NULL array next
+ * to a non-zero count; offsets that decrease; nc > 16; more than 4096 bytes of
+ * names; part[c] < -1 or > 255; cast[c] > 1; names that are not strictly
+ * ascending; a mode other than 0 and 1; out NULL. `sel` is a const cb_select*. */
+#define CB_SELECT_JSON 0
+#define CB_SELECT_META 1
+#define CB_ROW_TEXT 1
+#define CB_ROW_DEAD 2
+#define CB_ROW_ABSENT 4
+#define CB_ROW_BADJSON 8
+#define CB_ROW_EXTRA 16
+typedef struct cb_select {       /* host memory */
+  const uint8_t* cols; const uint64_t* col_off;  /* nc+1, non-decreasing */
+  const int32_t* part;                            /* nc: key part index, or -1 */
+  const uint8_t* cast;                            /* nc, nullable = zeros */
+  uint32_t nc;
+} cb_select;
+/* The entries of a result of any cb_tables_scan* call, skip per range of the
+ * result as in cb_scan_match. Synchronous, as cb_scan_match. An empty result
+ * gives a valid object whose text is [] or empty. */
+int cb_scan_select(const void* r, const uint32_t* skip /* one per range of r, nullable */,
+                   const void* sel /* cb_select */, int mode, void** out /* cb_rows */);
+/* Rows in DEVICE memory, e.g. what an enqueue-only cb_*get_many leaves (its
+ * keys as a ragged batch, its which, val_off and vals): row i's key is
+ * keys[key_off[i] .. key_off[i+1]), its value vals[val_off[i] ..
+ * val_off[i+1]); which[i] < 0 (which nullable: all present) says there is no
+ * row i. The work is enqueued on `stream`, behind whatever fills the buffers
+ * there, and the call waits for it twice: for the text's total length, from
+ * which the text is sized, and at the end, so the result is complete when the
+ * call returns. Host pointers are refused (CB_EINVAL). n == 0 touches no
+ * device. Two launches and a three-launch scan. */
+int cb_rows_select(const uint8_t* keys, const uint64_t* key_off /* n+1 */, const int32_t* which /* n, nullable */,
+                   const uint8_t* vals, const uint64_t* val_off /* n+1 */, uint64_t n, uint32_t skip,
+                   const void* sel /* cb_select */, int mode, int device, void* stream, void** out /* cb_rows */);
+/* Host only, no device: one row, e.g. a memtable row. *len = the length of the
+ * row's text (0 without text), *flags (nullable) its flags; the text is
+ * written to out when cap >= *len (call with out = NULL, cap = 0 to size). */
+int cb_row_select(const uint8_t* key, uint64_t key_len, uint32_t skip, const uint8_t* value, uint64_t value_len,
+                  const void* sel /* cb_select */, int mode, uint8_t* out, uint64_t cap, uint64_t* len,
+                  uint8_t* flags);
+/* Every output nullable: the rows, how many of them have text, the response's
+ * bytes. Host only. */
+int cb_rows_info(const void* rows, uint64_t* count, uint64_t* with_text, uint64_t* bytes);
+/* The response (text, `bytes` of it) and, per row, where its text lies in it
+ * (row_at, row_len: count uint64 each; row_len 0 without text) and its flags
+ * (count bytes), each nullable, into host or device memory. Synchronous; may
+ * be called any number of times. */
+int cb_rows_text(const void* rows, uint8_t* text, uint64_t* row_at, uint64_t* row_len, uint8_t* flags);
+/* Retires the result's memory through the block pool, as cb_scan_destroy. */
+int cb_rows_destroy(void* rows);
 /* Finalise a table from cb_sstable_create*: wait for its work, take its
  * results; returns its deferred error, if any. Idempotent, thread-safe. */
 int cb_table_wait(const cb_table* t);

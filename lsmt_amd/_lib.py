@@ -26,6 +26,8 @@ CB_EUTF8 = -7
 
 PATH_AUTO, PATH_DIRECT, PATH_TILED = 0, 1, 2
 XCHG_DENSE, XCHG_SPARSE = 0, 1
+SELECT_JSON, SELECT_META = 0, 1
+ROW_TEXT, ROW_DEAD, ROW_ABSENT, ROW_BADJSON, ROW_EXTRA = 1, 2, 4, 8, 16
 COMM_ID_BYTES = 128
 # cb_host_allgather_fn (include/cassbloom.h): int (*)(void* user, const void* send, void* recv, uint64_t bytes)
 HOST_ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
@@ -165,6 +167,12 @@ def load():
         "cb_tables_count_where": ([P, u32, u8p, P, u32, i32, P, P, i32, P, P, P], i32),
         "cb_scan_match": ([P, P, P, P], i32),
         "cb_row_matches": ([u8p, u64, u32, u8p, u64, P, ctypes.POINTER(i32)], i32),
+        "cb_scan_select": ([P, P, P, i32, pp], i32),
+        "cb_rows_select": ([u8p, P, P, u8p, P, u64, u32, P, i32, i32, P, pp], i32),
+        "cb_row_select": ([u8p, u64, u32, u8p, u64, P, i32, u8p, u64, pu64, u8p], i32),
+        "cb_rows_info": ([P, pu64, pu64, pu64], i32),
+        "cb_rows_text": ([P, u8p, P, P, u8p], i32),
+        "cb_rows_destroy": ([P], i32),
         "cb_scan_ranges": ([P, pu64, P], i32),
         "cb_key_prefix_end": ([u8p, u64, u8p, pu64, ctypes.POINTER(i32)], i32),
         "cb_scan_info": ([P, pu64, pu64, pu64, ctypes.POINTER(i32)], i32),

@@ -1,6 +1,7 @@
 // capi_merge.hpp — what the two users of the device merge share
 // (capi_merge.cpp: the merge itself, the table-list checks and compaction;
-// capi_scan.cpp: scans, counts and the scan result). Included only by them.
+// capi_scan.cpp: scans, counts and the scan result), and capi_select.cpp, which
+// stages its selection the way they stage theirs. Included only by them.
 #pragma once
 #include "capi_table.hpp"
 #include "compact.hpp"

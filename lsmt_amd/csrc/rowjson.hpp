@@ -117,7 +117,7 @@ inline void where_pack(const uint8_t* cols, const uint64_t* col_off, const uint8
   for (uint32_t i = nc; i <= kWhereMaxConds; ++i) w->val_at[i] = (uint16_t)at;
 }
 
-// ---- byte sources: size(), seek(i <= size()), more(), next() ----
+// ---- byte sources: size(), seek(i <= size()), tell(), more(), next() ----
 
 // Decoded bytes p[0..n).
 struct DecodedBytes {
@@ -126,6 +126,7 @@ struct DecodedBytes {
   CB_ROW_HD DecodedBytes(const uint8_t* p_, uint64_t n_) : p(p_), n(n_), i(0) {}
   CB_ROW_HD uint64_t size() const { return n; }
   CB_ROW_HD void seek(uint64_t at) { i = at; }
+  CB_ROW_HD uint64_t tell() const { return i; }
   CB_ROW_HD bool more() const { return i < n; }
   CB_ROW_HD uint8_t next() { return p[i++]; }
 };
@@ -164,6 +165,7 @@ struct B64Bytes {
     if (at < n) load();
     else r = 3;
   }
+  CB_ROW_HD uint64_t tell() const { return i; }
   CB_ROW_HD bool more() const { return i < n; }
   CB_ROW_HD uint8_t next() {
     if (r == 3) {
@@ -178,47 +180,45 @@ struct B64Bytes {
   }
 };
 
-// ---- the rule ----
+// ---- the key's parts ----
 
-// The conditions the key answers (*answered) and, returned, those of them it
-// satisfies, for the key's parts after `skip` bytes.
-CB_ROW_HD inline uint32_t where_key_conditions(const WherePred& w, const uint8_t* key, uint64_t klen, uint32_t skip,
-                                               uint32_t* answered) {
-  const uint64_t s = skip < klen ? skip : klen;
-  const uint8_t* rest = key + s;
-  const uint64_t n = klen - s;
-  uint32_t ans = 0, sat = 0;
-  bool counted = false;
+// How many parts the key's rest[0..n) has: one more than its separators (an
+// empty rest is one empty part).
+CB_ROW_HD inline uint64_t key_part_count(const uint8_t* rest, uint64_t n) {
   uint64_t nparts = 1;
-  for (uint32_t i = 0; i < w.nc; ++i) {
-    const int32_t p = w.part[i];
-    if (p < 0) continue;
-    if (!counted) {
-      for (uint64_t j = 0; j < n; ++j) nparts += rest[j] == '|';
-      counted = true;
-    }
-    if ((uint64_t)p >= nparts) continue;
-    ans |= 1u << i;
-    uint64_t a = 0;  // part p begins after its p-th '|' (there are at least p)
-    for (int32_t k = 0; k < p; ++k) {
-      while (rest[a] != '|') ++a;
-      ++a;
-    }
-    const uint32_t vat = w.val_at[i], vlen = w.val_at[i + 1] - vat;
-    uint64_t j = 0;
-    while (a + j < n && rest[a + j] != '|' && j < vlen && rest[a + j] == w.bytes[vat + j]) ++j;
-    if (j == vlen && (a + j == n || rest[a + j] == '|')) sat |= 1u << i;
-  }
-  *answered = ans;
-  return sat;
+  for (uint64_t j = 0; j < n; ++j) nparts += rest[j] == '|';
+  return nparts;
 }
 
-// The conditions of `ask` (a mask over w's conditions) that the map of the
-// document src.next()... satisfies; 0 for a document with an error. The pairs
-// are compared as they are read: per string, `alive` holds the conditions
-// whose name (or value) equals the unescaped bytes so far.
-template <class Src>
-CB_ROW_HD inline uint32_t where_json_conditions(const WherePred& w, uint32_t ask, Src& src) {
+// Where part p < key_part_count(rest, n) begins in rest, and *len its length.
+CB_ROW_HD inline uint64_t key_part_at(const uint8_t* rest, uint64_t n, uint32_t p, uint64_t* len) {
+  uint64_t a = 0;  // part p begins after its p-th separator (there are at least p)
+  for (uint32_t k = 0; k < p; ++k) {
+    while (rest[a] != '|') ++a;
+    ++a;
+  }
+  uint64_t e = a;
+  while (e < n && rest[e] != '|') ++e;
+  *len = e - a;
+  return a;
+}
+
+// ---- the grammar ----
+
+// The one reader of the map's grammar (the header's "Map" paragraph): the
+// document src.next()... is walked once, and what it holds goes to a sink:
+//   sink.begin(value, at)  a string begins: a name, or (value) a name's value;
+//                          `at` is the source's place after the opening quote
+//   sink.byte(b)           one byte of the string, unescaped
+//   sink.end(value)        the string is complete (it is valid so far)
+//   sink.done(valid)       the input is at its end, or failed: whether the
+//                          document is a valid map. An error ANYWHERE makes
+//                          everything handed out before void.
+// Returns `valid`. With one_string the source stands after an opening quote
+// (an `at` of an earlier walk of a valid document): that string alone is read,
+// sink.byte() for its bytes, and nothing else is called.
+template <class Src, class Sink>
+CB_ROW_HD inline bool json_walk(Src& src, Sink& sink, bool one_string = false) {
   enum : uint32_t {
     kOpen,       // ws, then {
     kFirstKey,   // ws, then " or }
@@ -234,39 +234,33 @@ CB_ROW_HD inline uint32_t where_json_conditions(const WherePred& w, uint32_t ask
     kLowU,       // ... and its u
     kFail
   };
-  uint32_t st = kOpen, alive = 0, keyhit = 0, ok = 0, pos = 0;
+  uint32_t st = one_string ? kStr : kOpen;
   uint32_t need = 0, lo = 0x80, hi = 0xBF;  // continuation bytes still due, and the next one's bounds
   uint32_t cp = 0, hexn = 0, high = 0;
   bool val = false;
-  auto emit = [&](uint32_t b) {  // one unescaped byte of the current string
-    for (uint32_t m = alive; m; m &= m - 1) {
-      const uint32_t i = (uint32_t)__builtin_ctz(m);
-      const uint32_t at = val ? w.val_at[i] : w.col_at[i], len = (val ? w.val_at[i + 1] : w.col_at[i + 1]) - at;
-      if (pos >= len || w.bytes[at + pos] != b) alive &= ~(1u << i);
-    }
-    ++pos;
-  };
+  uint32_t out = 0, nout = 0;  // the string's bytes that an input byte completes: nout of them, the first in out's low byte
   auto emit_cp = [&](uint32_t c) {  // a code point from an escape, as UTF-8
     if (c < 0x80) {
-      emit(c);
+      out = c;
+      nout = 1;
     } else if (c < 0x800) {
-      emit(0xC0 | c >> 6);
-      emit(0x80 | (c & 63));
+      out = (0xC0 | c >> 6) | (0x80 | (c & 63)) << 8;
+      nout = 2;
     } else if (c < 0x10000) {
-      emit(0xE0 | c >> 12);
-      emit(0x80 | (c >> 6 & 63));
-      emit(0x80 | (c & 63));
+      out = (0xE0 | c >> 12) | (0x80 | (c >> 6 & 63)) << 8 | (0x80 | (c & 63)) << 16;
+      nout = 3;
     } else {
-      emit(0xF0 | c >> 18);
-      emit(0x80 | (c >> 12 & 63));
-      emit(0x80 | (c >> 6 & 63));
-      emit(0x80 | (c & 63));
+      out = (0xF0 | c >> 18) | (0x80 | (c >> 12 & 63)) << 8 | (0x80 | (c >> 6 & 63)) << 16 | (0x80 | (c & 63)) << 24;
+      nout = 4;
     }
+  };
+  auto emit = [&](uint32_t b) {
+    out = b;
+    nout = 1;
   };
   auto begin = [&](bool value) {
     val = value;
-    alive = value ? keyhit : ask;
-    pos = 0;
+    sink.begin(value, src.tell());
     st = kStr;
   };
   auto is_ws = [](uint32_t c) { return c == ' ' || c == '\t' || c == '\n' || c == '\r'; };
@@ -306,19 +300,10 @@ CB_ROW_HD inline uint32_t where_json_conditions(const WherePred& w, uint32_t ask
           lo = 0x80;
           hi = 0xBF;
           emit(c);
-        } else if (c == '"') {  // the string ends: the conditions of exactly this length stay
-          for (uint32_t m = alive; m; m &= m - 1) {
-            const uint32_t i = (uint32_t)__builtin_ctz(m);
-            const uint32_t len = val ? w.val_at[i + 1] - w.val_at[i] : w.col_at[i + 1] - w.col_at[i];
-            if (len != pos) alive &= ~(1u << i);
-          }
-          if (val) {
-            ok = (ok & ~keyhit) | alive;  // the last pair of a name wins
-            st = kNext;
-          } else {
-            keyhit = alive;
-            st = kColon;
-          }
+        } else if (c == '"') {
+          if (one_string) return true;
+          sink.end(val);
+          st = val ? kNext : kColon;
         } else if (c == '\\') {
           st = kEsc;
         } else if (c < 0x20) {
@@ -400,8 +385,87 @@ CB_ROW_HD inline uint32_t where_json_conditions(const WherePred& w, uint32_t ask
       default:
         st = kFail;
     }
+    for (; nout; --nout, out >>= 8) sink.byte(out & 0xFF);  // (the one place a sink gets bytes)
   }
-  return st == kEnd ? ok : 0;
+  if (one_string) return false;  // (an `at` that is none: the string never closed)
+  sink.done(st == kEnd);
+  return st == kEnd;
+}
+
+// ---- the rule ----
+
+// The conditions the key answers (*answered) and, returned, those of them it
+// satisfies, for the key's parts after `skip` bytes.
+CB_ROW_HD inline uint32_t where_key_conditions(const WherePred& w, const uint8_t* key, uint64_t klen, uint32_t skip,
+                                               uint32_t* answered) {
+  const uint64_t s = skip < klen ? skip : klen;
+  const uint8_t* rest = key + s;
+  const uint64_t n = klen - s;
+  uint32_t ans = 0, sat = 0;
+  bool counted = false;
+  uint64_t nparts = 1;
+  for (uint32_t i = 0; i < w.nc; ++i) {
+    const int32_t p = w.part[i];
+    if (p < 0) continue;
+    if (!counted) {
+      nparts = key_part_count(rest, n);
+      counted = true;
+    }
+    if ((uint64_t)p >= nparts) continue;
+    ans |= 1u << i;
+    uint64_t plen = 0;
+    const uint64_t a = key_part_at(rest, n, (uint32_t)p, &plen);
+    const uint32_t vat = w.val_at[i], vlen = w.val_at[i + 1] - vat;
+    uint64_t j = 0;
+    while (j < plen && j < vlen && rest[a + j] == w.bytes[vat + j]) ++j;
+    if (j == vlen && j == plen) sat |= 1u << i;
+  }
+  *answered = ans;
+  return sat;
+}
+
+// json_walk's sink for the conditions: the pairs are compared as they are
+// read; per string, `alive` holds the conditions whose name (or value) equals
+// the unescaped bytes so far.
+struct WhereSink {
+  const WherePred& w;
+  uint32_t ask, alive, keyhit, ok, pos;
+  bool val;
+  CB_ROW_HD WhereSink(const WherePred& w_, uint32_t ask_) : w(w_), ask(ask_), alive(0), keyhit(0), ok(0), pos(0), val(false) {}
+  CB_ROW_HD void begin(bool value, uint64_t) {
+    val = value;
+    alive = value ? keyhit : ask;
+    pos = 0;
+  }
+  CB_ROW_HD void byte(uint32_t b) {
+    for (uint32_t m = alive; m; m &= m - 1) {
+      const uint32_t i = (uint32_t)__builtin_ctz(m);
+      const uint32_t at = val ? w.val_at[i] : w.col_at[i], len = (val ? w.val_at[i + 1] : w.col_at[i + 1]) - at;
+      if (pos >= len || w.bytes[at + pos] != b) alive &= ~(1u << i);
+    }
+    ++pos;
+  }
+  CB_ROW_HD void end(bool) {  // the conditions of exactly this length stay
+    for (uint32_t m = alive; m; m &= m - 1) {
+      const uint32_t i = (uint32_t)__builtin_ctz(m);
+      const uint32_t len = val ? w.val_at[i + 1] - w.val_at[i] : w.col_at[i + 1] - w.col_at[i];
+      if (len != pos) alive &= ~(1u << i);
+    }
+    if (val) ok = (ok & ~keyhit) | alive;  // the last pair of a name wins
+    else keyhit = alive;
+  }
+  CB_ROW_HD void done(bool valid) {
+    if (!valid) ok = 0;
+  }
+};
+
+// The conditions of `ask` (a mask over w's conditions) that the map of the
+// document src.next()... satisfies; 0 for a document with an error.
+template <class Src>
+CB_ROW_HD inline uint32_t where_json_conditions(const WherePred& w, uint32_t ask, Src& src) {
+  WhereSink sink(w, ask);
+  json_walk(src, sink);
+  return sink.ok;
 }
 
 // Whether the row (key, value) matches w, the key's parts taken after `skip`

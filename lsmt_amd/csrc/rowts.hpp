@@ -32,6 +32,18 @@ constexpr uint64_t decoded_ts(const uint8_t* p, uint64_t len) {
   return v;
 }
 
+// The same through a byte source over the decoded value (rowjson.hpp's
+// sources: size(), seek(), next()), which is left at the payload's first byte:
+// split_ts's second half begins there.
+template <class Src>
+constexpr uint64_t source_ts(Src& value) {
+  const bool has = value.size() >= 8;
+  value.seek(0);
+  uint64_t v = 0;
+  for (uint32_t j = 0; has && j < 8; ++j) v = v << 8 | value.next();
+  return v;
+}
+
 // The same from a value's base64 text, vdl its decoded length (the line
 // index's; not kBadValue: callers test that first). Such a text is valid
 // STANDARD base64 and holds at least 12 characters when vdl >= 8, so its
