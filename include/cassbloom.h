@@ -58,6 +58,7 @@ extern "C" {
 #define CB_EDECODE (-5) /* malformed BloomProto bytes */
 #define CB_ENODEV (-6)  /* no usable gfx950 device */
 #define CB_EUTF8 (-7)   /* a data-file key is not UTF-8: SsTable::load returns Err */
+#define CB_EBASE64 (-8) /* a log record's value is not STANDARD base64: Wal::new returns Err */
 
 typedef struct cb_filter cb_filter;
 typedef struct cb_filterset cb_filterset; /* bit-sliced filter sets, see below */
@@ -964,6 +965,57 @@ int cb_set_probe_pack_fixed(const cb_filterset* set, const uint8_t* keys, uint32
                             uint64_t* hits, uint32_t* pack, uint64_t cap, void* stream);
 int cb_hits_expand_set(const uint32_t* packs, uint32_t nranks, uint64_t cap, const uint64_t* row_off, uint64_t n,
                        uint64_t total_rows, uint64_t* full, uint32_t* ok, void* stream);
+
+/* ---- the write-ahead log replayed on the device ---- */
+/* What cb_log_replay saw of a log. lines counts the non-empty pieces of the
+ * split on '\n', entries those of them with a TAB, keys the distinct keys
+ * among the entries (the lines of the table). After CB_EUTF8 / CB_EBASE64
+ * bad_line is the first failing piece's index among the non-empty pieces and
+ * bad_offset its first byte's offset in the log (lines and entries then count
+ * the whole log, keys is 0); UINT64_MAX otherwise. */
+typedef struct {
+    uint64_t lines;      /* non-empty pieces */
+    uint64_t entries;    /* of those with a TAB */
+    uint64_t keys;       /* distinct keys = lines of the table */
+    uint64_t bad_line;   /* UINT64_MAX, or index among the non-empty pieces */
+    uint64_t bad_offset; /* UINT64_MAX, or byte offset of that piece */
+} cb_log_stats;
+/* Database::new's replay of the write-ahead log (src/lib.rs:30-39: Wal::new's
+ * parse_entries, src/wal.rs:14-31, then one memtable.insert per record in log
+ * order) followed by the flush of that memtable (SsTable::create,
+ * src/sstable.rs:51-87), on the device: the table holds one line per distinct
+ * key, the LAST record of that key, sorted by key bytes. A record is what
+ * insert_internal appends (src/lib.rs:96-102), `key \t STANDARD.encode(value)
+ * \n`, byte for byte a table line, so its text is copied, never re-encoded.
+ * The log is split on 0x0A; empty pieces are skipped, the last piece counts
+ * without a final newline, and a non-empty piece without a TAB is skipped
+ * whatever its bytes (parse_entries never looks at it). Of any other piece
+ * the bytes before the first TAB are the key (it may be empty) and must be
+ * UTF-8 by std::str::from_utf8, the bytes after it up to the piece's end the
+ * value's text, which base64 0.21.7 STANDARD.decode must accept (empty text is
+ * the empty value; a second TAB is part of the text and fails it). '\r' is a
+ * byte like any other. The first failing piece in log order fails the call,
+ * its key checked before its value (the `?` order of src/wal.rs:21-26):
+ * CB_EUTF8 or CB_EBASE64 (tests/wal_error_test.rs:19), nothing is returned,
+ * the outputs are cleared and *stats, when given, names the piece. The rule
+ * is lsmt_amd/csrc/logline.hpp's. A last write that is a tombstone (8
+ * timestamp bytes only) stays as a line, as it stays in the memtable.
+ * log: host or device memory. *bloom_out (nullable): BloomFilter::new(m_bits)
+ * with every kept key inserted (src/sstable.rs:59-63); the zone map is the
+ * first and last kept key (cb_table_zone). The table is finalised and
+ * well-formed, as one from cb_tables_compact; a log without an entry gives the
+ * table of length 0. CB_EINVAL: table_out NULL, log NULL with len > 0, a piece
+ * of 4 GiB or more, 2^32 or more entries. CB_EZEROM: m_bits == 0 with
+ * bloom_out given, checked before the log is looked at. The call waits for its
+ * own stream (the output's size depends on the data), never for the device. */
+int cb_log_replay(const uint8_t* log, uint64_t len, uint64_t m_bits, int device, void* stream,
+                  cb_table** table_out, cb_filter** bloom_out /* nullable */, void* stats /* cb_log_stats, nullable */);
+/* The verdict of one piece of a log (no '\n' inside: CB_EINVAL) by the same
+ * rule (parse_entries' loop body, src/wal.rs:17-28): *kind = 0 skipped (no
+ * TAB, or empty), 1 an entry, CB_EUTF8 or CB_EBASE64; for an entry *key_len
+ * (nullable) is the key's length and *value_len (nullable) the value's
+ * decoded length, 0 both otherwise. Host only, no device access. */
+int cb_log_line(const uint8_t* piece, uint64_t len, int* kind, uint64_t* key_len, uint64_t* value_len);
 
 /* ---- tuning / introspection (bench + tests) ---- */
 /* Path selection: 0 = auto, 1 = force direct (per-key atomics / gathers),

@@ -28,6 +28,10 @@ from .bloom import (  # noqa: E402
     probe_tiers,
     sstable_create,
     compact,
+    replay_log,
+    log_line,
+    wal_bytes,
+    LogStats,
     scan,
     scan_many,
     count,
@@ -52,5 +56,5 @@ from .bloom import (  # noqa: E402
 
 __all__ = ["BloomFilter", "BloomProto", "DeviceKeys", "FilterSet", "insert_many", "KeyBatch", "device_count", "last_path",
            "probe", "set_dense", "set_path", "unpack_hits", "zone_bounds", "ZoneMap", "TableMeta", "Table", "get_many", "sstable_create",
-           "compact", "scan", "scan_many", "count", "scan_live", "compact_live", "compact_lww", "scan_lww", "count_lww", "count_where", "row_matches", "select_rows", "row_select", "RowsResult", "prefix_end", "ScanResult", "probe_tiers", "get_many_tiers", "hits_compress", "hits_expand", "hits_expand_set"]
+           "compact", "replay_log", "log_line", "wal_bytes", "LogStats", "scan", "scan_many", "count", "scan_live", "compact_live", "compact_lww", "scan_lww", "count_lww", "count_where", "row_matches", "select_rows", "row_select", "RowsResult", "prefix_end", "ScanResult", "probe_tiers", "get_many_tiers", "hits_compress", "hits_expand", "hits_expand_set"]
 __version__ = "0.1.0"

@@ -23,6 +23,7 @@ CB_EHIP = -4
 CB_EDECODE = -5
 CB_ENODEV = -6
 CB_EUTF8 = -7
+CB_EBASE64 = -8
 
 PATH_AUTO, PATH_DIRECT, PATH_TILED = 0, 1, 2
 XCHG_DENSE, XCHG_SPARSE = 0, 1
@@ -50,6 +51,15 @@ class ZoneBounds(ctypes.Structure):
     """struct cb_zone_bounds (include/cassbloom.h)."""
     _fields_ = [("min", ctypes.c_void_p), ("min_len", ctypes.c_uint64), ("has_min", ctypes.c_int),
                 ("max", ctypes.c_void_p), ("max_len", ctypes.c_uint64), ("has_max", ctypes.c_int)]
+
+
+class LogStats(ctypes.Structure):
+    """struct cb_log_stats (include/cassbloom.h)."""
+    _fields_ = [("lines", ctypes.c_uint64), ("entries", ctypes.c_uint64), ("keys", ctypes.c_uint64),
+                ("bad_line", ctypes.c_uint64), ("bad_offset", ctypes.c_uint64)]
+
+    def __repr__(self):
+        return "LogStats(%s)" % ", ".join("%s=%d" % (n, getattr(self, n)) for n, _ in self._fields_)
 
 
 class MetaInfo(ctypes.Structure):
@@ -183,6 +193,8 @@ def load():
         "cb_table_wait": ([P], i32),
         "cb_table_zone": ([P, i32, u8p, u64, pu64], i32),
         "cb_table_rebuild": ([P, u64, P, pp, pu64, pu64], i32),
+        "cb_log_replay": ([u8p, u64, u64, i32, P, pp, pp, P], i32),
+        "cb_log_line": ([u8p, u64, ctypes.POINTER(i32), pu64, pu64], i32),
         "cb_table_well_formed": ([P, ctypes.POINTER(i32)], i32),
         "cb_table_force_exact": ([i32], i32),
         "cb_table_bucket_limit": ([u64], i32),

@@ -4,8 +4,9 @@
 // runs the same steps with the select that drops tombstones (liverow.hpp),
 // cb_tables_compact_lww with the select that keeps a key's line of the
 // greatest timestamp (rowts.hpp) in place of its newest one. The merge's
-// other user, the scans and counts, is capi_scan.cpp; capi_merge.hpp declares
-// what both need.
+// other user, the scans and counts, is capi_scan.cpp, and the log replay
+// (capi_replay.cpp) runs it over its own gather and then takes compaction's
+// steps behind it; capi_merge.hpp declares what they need.
 //
 // Reference: src/sstable.rs:51-98 (the file a compaction writes),
 // src/lib.rs:125-146 (Database::get, whose answers it reproduces), src/cluster.rs:405-416,
@@ -58,14 +59,14 @@ int merge_alloc(uint32_t nsrc_cap, uint64_t n, uint64_t kbound, MergeOrder order
   m->ts = order == MergeOrder::lww ? (uint64_t*)tmp.at(o_ts) : nullptr;
   return CB_OK;
 }
-int enqueue_merge_select(const Merge& m, const cb::CompactSrc* dsrc, uint32_t nsrc, MergeRule rule, hipStream_t s) {
-  const uint64_t n = m.n;
-  HIP_TRY(cb::launch_compact_klen(dsrc, nsrc, n, m.klen, s));
-  HIP_TRY(cb::launch_scan_u64(m.klen, m.ko, n, m.scan, s));
+int enqueue_sort_begin(const Merge& m, hipStream_t s) {
   // the bin sort's inputs: an unsorted batch (flags[0]) and its prefix byte masks
   HIP_TRY(hipMemsetAsync(m.dr, 0, cb::kCreateHead, s));
   HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)&m.dr->flags[0], 1, 1, s));
-  HIP_TRY(cb::launch_compact_gather(dsrc, nsrc, n, m.ko, m.kb, m.side, &m.dr->dmask[0][0], s));
+  return CB_OK;
+}
+int enqueue_sort_select(const Merge& m, MergeRule rule, hipStream_t s) {
+  const uint64_t n = m.n;
   // the stable sort by key, input index last: a key's lines leave it
   // adjacent, newest first
   if (int rc = enqueue_key_sort(m.plan, m.kb, m.ko, n, m.order, m.sort, m.dr, s, nullptr, nullptr, nullptr)) return rc;
@@ -80,56 +81,32 @@ int enqueue_merge_select(const Merge& m, const cb::CompactSrc* dsrc, uint32_t ns
                                         m.tbytes, m.tkeys, s));
   return CB_OK;
 }
-int enqueue_merge(const Merge& m, const cb::CompactSrc* dsrc, uint32_t nsrc, MergeRule rule, hipStream_t s,
-                  uint64_t (&h)[3]) {
+int enqueue_merge_select(const Merge& m, const cb::CompactSrc* dsrc, uint32_t nsrc, MergeRule rule, hipStream_t s) {
   const uint64_t n = m.n;
-  if (int rc = enqueue_merge_select(m, dsrc, nsrc, rule, s)) return rc;
+  HIP_TRY(cb::launch_compact_klen(dsrc, nsrc, n, m.klen, s));
+  HIP_TRY(cb::launch_scan_u64(m.klen, m.ko, n, m.scan, s));
+  if (int rc = enqueue_sort_begin(m, s)) return rc;
+  HIP_TRY(cb::launch_compact_gather(dsrc, nsrc, n, m.ko, m.kb, m.side, &m.dr->dmask[0][0], s));
+  return enqueue_sort_select(m, rule, s);
+}
+int merge_totals(const Merge& m, hipStream_t s, uint64_t (&h)[3]) {
   HIP_TRY(cb::launch_tile_scan(m.tcnt, m.tiles, m.tot + 0, s));
   HIP_TRY(cb::launch_tile_scan(m.tbytes, m.tiles, m.tot + 1, s));
   HIP_TRY(cb::launch_tile_scan(m.tkeys, m.tiles, m.tot + 2, s));
   h[0] = h[1] = h[2] = 0;
   HIP_TRY(hipMemcpyAsync(h, m.tot, sizeof h, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
-  if (h[0] > n || h[2] > m.kbound || h[1] > m.kbound + n) return fail(CB_EHIP, "merge: inconsistent totals");
+  if (h[0] > m.n || h[2] > m.kbound || h[1] > m.kbound + m.n) return fail(CB_EHIP, "merge: inconsistent totals");
   return CB_OK;
 }
-
-}  // namespace cbx
-
-namespace {
-
-// ---- cb_tables_compact's steps, in the order it takes them ----
-
-// The kept keys as one batch (device, in a block of the call's).
-struct KeptKeys {
-  uint8_t* kb = nullptr;
-  uint64_t* ko = nullptr;
-};
-
-// 1: the sources: the non-empty tables, newest first, with their line bases;
-// n their lines, kbound a bound on their keys' bytes.
-int compact_sources(const cb_table* const* tables, uint32_t nt, std::vector<cb::CompactSrc>& srcs, uint64_t* n,
-                    uint64_t* kbound) {
-  if (int rc = for_live_tables(tables, nt, [&](cb_table* ti, uint32_t) {
-        srcs.push_back(cb::CompactSrc{ti->data, ti->rec, ti->llen, *n});
-        *n += ti->nlines;
-        *kbound += ti->len;  // the keys' bytes are among the file's
-      }))
-    return rc;
-  if (*n > 0xFFFFFFFFull) return fail(CB_EINVAL, "too many lines for one compaction");
-  return CB_OK;
+int enqueue_merge(const Merge& m, const cb::CompactSrc* dsrc, uint32_t nsrc, MergeRule rule, hipStream_t s,
+                  uint64_t (&h)[3]) {
+  if (int rc = enqueue_merge_select(m, dsrc, nsrc, rule, s)) return rc;
+  return merge_totals(m, s, h);
 }
 
-// 2: the merge over the sources, staged into its scratch (one wait: the
-// source is pageable), up to the survivors' totals h (enqueue_merge's wait).
-int merge_sources(const std::vector<cb::CompactSrc>& srcs, uint64_t n, uint64_t kbound, MergeRule rule,
-                  TempBlock& tmp, Merge* mg, hipStream_t s, uint64_t (&h)[3]) {
-  const uint32_t nsrc = (uint32_t)srcs.size();
-  if (int rc = merge_alloc(nsrc, n, kbound, rule.order, tmp, mg)) return rc;
-  HIP_TRY(hipMemcpyAsync(mg->dsrc, srcs.data(), nsrc * sizeof(cb::CompactSrc), hipMemcpyHostToDevice, s));
-  HIP_TRY(hipStreamSynchronize(s));  // the source is pageable
-  return enqueue_merge(*mg, mg->dsrc, nsrc, rule, s, h);
-}
+// ---- what a maker of a merged table does after the merge (cb_tables_compact's steps 3 and 5;
+// cb_log_replay takes the same) ----
 
 // 3: the survivors (h = {lines, file bytes, key bytes}) formatted into t: the
 // file and its line index in one pass (the file is not re-read), and the kept
@@ -180,6 +157,37 @@ int finish_compacted(cb_table* t, const Merge& mg, const KeptKeys& k, const uint
 
 // A filter of no bits: BloomFilter::insert's `% 0` (src/bloom.rs:36).
 int zero_m_error() { return fail(CB_EZEROM, "attempt to calculate the remainder with a divisor of zero"); }
+
+}  // namespace cbx
+
+namespace {
+
+// ---- cb_tables_compact's steps, in the order it takes them ----
+
+// 1: the sources: the non-empty tables, newest first, with their line bases;
+// n their lines, kbound a bound on their keys' bytes.
+int compact_sources(const cb_table* const* tables, uint32_t nt, std::vector<cb::CompactSrc>& srcs, uint64_t* n,
+                    uint64_t* kbound) {
+  if (int rc = for_live_tables(tables, nt, [&](cb_table* ti, uint32_t) {
+        srcs.push_back(cb::CompactSrc{ti->data, ti->rec, ti->llen, *n});
+        *n += ti->nlines;
+        *kbound += ti->len;  // the keys' bytes are among the file's
+      }))
+    return rc;
+  if (*n > 0xFFFFFFFFull) return fail(CB_EINVAL, "too many lines for one compaction");
+  return CB_OK;
+}
+
+// 2: the merge over the sources, staged into its scratch (one wait: the
+// source is pageable), up to the survivors' totals h (enqueue_merge's wait).
+int merge_sources(const std::vector<cb::CompactSrc>& srcs, uint64_t n, uint64_t kbound, MergeRule rule,
+                  TempBlock& tmp, Merge* mg, hipStream_t s, uint64_t (&h)[3]) {
+  const uint32_t nsrc = (uint32_t)srcs.size();
+  if (int rc = merge_alloc(nsrc, n, kbound, rule.order, tmp, mg)) return rc;
+  HIP_TRY(hipMemcpyAsync(mg->dsrc, srcs.data(), nsrc * sizeof(cb::CompactSrc), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipStreamSynchronize(s));  // the source is pageable
+  return enqueue_merge(*mg, mg->dsrc, nsrc, rule, s, h);
+}
 
 // The live-row and LWW compactions check their own arguments before they look
 // at the table list (compact_tables looks at the list first): a filter of no

@@ -1,7 +1,8 @@
 // capi_merge.hpp — what the two users of the device merge share
 // (capi_merge.cpp: the merge itself, the table-list checks and compaction;
-// capi_scan.cpp: scans, counts and the scan result), and capi_select.cpp, which
-// stages its selection the way they stage theirs. Included only by them.
+// capi_scan.cpp: scans, counts and the scan result), capi_select.cpp, which
+// stages its selection the way they stage theirs, and capi_replay.cpp, whose
+// log replay is the merge over one unsorted input. Included only by them.
 #pragma once
 #include "capi_table.hpp"
 #include "compact.hpp"
@@ -57,6 +58,15 @@ int merge_alloc(uint32_t nsrc_cap, uint64_t n, uint64_t kbound, cb::MergeOrder o
 // lines' timestamps and the two launches of the LWW select (m was allocated
 // for the same order); drop_dead: either keeps no tombstone (liverow.hpp).
 int enqueue_merge_select(const Merge& m, const cb::CompactSrc* dsrc, uint32_t nsrc, cb::MergeRule rule, hipStream_t s);
+// enqueue_merge_select's two halves around its gather, for a caller that
+// gathers its own records into m (cb_log_replay, capi_replay.cpp): the bin
+// sort's inputs reset (an unsorted batch, its prefix byte masks zeroed) before
+// the gather, and behind it the sort and the rule's select.
+int enqueue_sort_begin(const Merge& m, hipStream_t s);
+int enqueue_sort_select(const Merge& m, cb::MergeRule rule, hipStream_t s);
+// enqueue_merge's tail: the scans of the tile sums, the totals read back,
+// waited for and checked.
+int merge_totals(const Merge& m, hipStream_t s, uint64_t (&h)[3]);
 // The rest of the merge for a caller that writes the survivors out: the scans
 // of the tile sums and the survivors' totals h = {lines, file bytes, key
 // bytes}, read back (they size the caller's output), the stream waited for,
@@ -64,6 +74,25 @@ int enqueue_merge_select(const Merge& m, const cb::CompactSrc* dsrc, uint32_t ns
 // (A count stops at the select: it places no survivor.)
 int enqueue_merge(const Merge& m, const cb::CompactSrc* dsrc, uint32_t nsrc, cb::MergeRule rule, hipStream_t s,
                   uint64_t (&h)[3]);
+
+// ---- the merged table (capi_merge.cpp: cb_tables_compact's steps behind the merge, which
+// cb_log_replay takes too) ----
+
+// The kept keys as one batch (device, in a block of the call's).
+struct KeptKeys {
+  uint8_t* kb = nullptr;
+  uint64_t* ko = nullptr;
+};
+// The survivors (h = {lines, file bytes, key bytes}) formatted into t: the
+// file and its line index in one pass, and the kept keys beside them (in
+// `keys`). No survivor: the file's buffer alone.
+int format_survivors(cb_table* t, const Merge& mg, const uint64_t (&h)[3], TempBlock& keys, KeptKeys* k,
+                     hipStream_t s);
+// The directory and the zone map's bounds of a formatted table with at least
+// one line (two waits); t is well-formed by construction.
+int finish_compacted(cb_table* t, const Merge& mg, const KeptKeys& k, const uint64_t (&h)[3], hipStream_t s);
+// A filter of no bits: BloomFilter::insert's `% 0` (src/bloom.rs:36).
+int zero_m_error();
 
 // ---- host values on their way into a call's scratch block ----
 

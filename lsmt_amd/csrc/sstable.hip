@@ -14,6 +14,7 @@
 
 #include "blockscan.hpp"
 #include "launch.hpp"
+#include "logline.hpp"
 #include "profile.hpp"
 #include "sstable.hpp"
 #include "tablesearch.hpp"
@@ -219,37 +220,9 @@ hipError_t launch_line_keys(const uint8_t* data, uint64_t nlines, LineRec* rec, 
 
 namespace {
 
-// Rust's str::from_utf8 acceptance (Unicode well-formed sequences: no
-// overlongs, no surrogates, nothing above U+10FFFF).
-__device__ __forceinline__ bool utf8_valid(const uint8_t* p, uint64_t n) {
-  uint64_t i = 0;
-  while (i < n) {
-    const uint32_t c = p[i];
-    if (c < 0x80) {
-      ++i;
-      continue;
-    }
-    uint32_t len, lo = 0x80, hi = 0xBF;
-    if (c >= 0xC2 && c <= 0xDF) len = 2;
-    else if (c == 0xE0) { len = 3; lo = 0xA0; }
-    else if ((c >= 0xE1 && c <= 0xEC) || c == 0xEE || c == 0xEF) len = 3;
-    else if (c == 0xED) { len = 3; hi = 0x9F; }
-    else if (c == 0xF0) { len = 4; lo = 0x90; }
-    else if (c >= 0xF1 && c <= 0xF3) len = 4;
-    else if (c == 0xF4) { len = 4; hi = 0x8F; }
-    else return false;
-    if (n - i < len) return false;
-    if (p[i + 1] < lo || p[i + 1] > hi) return false;
-    for (uint32_t k = 2; k < len; ++k)
-      if (p[i + k] < 0x80 || p[i + k] > 0xBF) return false;
-    i += len;
-  }
-  return true;
-}
-
 // Per line: has[l] = 1 when the line has a TAB (its key is inserted), klen[l]
 // = the key's bytes (0 otherwise); *bad = the first line whose key is not
-// UTF-8 (the reference's load returns Err there).
+// UTF-8 (the reference's load returns Err there; utf8_valid is logline.hpp's).
 __global__ __launch_bounds__(kNT) void k_rebuild_mark(const uint8_t* __restrict__ data,
                                                       const LineRec* __restrict__ rec, uint64_t nlines,
                                                       uint64_t* __restrict__ has, uint64_t* __restrict__ klen,
