@@ -17,6 +17,14 @@ all-gather (``Comm.host``: e.g. gloo between processes sharing one GPU).
 """
 from __future__ import annotations
 
+import ctypes
+import traceback
+
+import numpy as np
+
+from . import _lib
+from ._ffi import _Handle, _L, _ptr_of, _stream
+
 
 def shard_range(n_total: int, world: int, rank: int) -> tuple[int, int]:
     """Contiguous [lo, hi) of the filters owned by `rank` (sizes differ by <= 1)."""
@@ -50,15 +58,12 @@ def pack_words(nw: int, cap: int) -> int:
 
 def comm_shard(n_total: int, world: int, rank: int) -> tuple[int, int]:
     """The C ABI's split (cb_comm_shard): must equal shard_range."""
-    import ctypes
-
-    from . import _lib
     lo, cnt = ctypes.c_uint64(), ctypes.c_uint64()
-    _lib.check(_lib.load().cb_comm_shard(n_total, world, rank, ctypes.byref(lo), ctypes.byref(cnt)))
+    _lib.check(_L().cb_comm_shard(n_total, world, rank, ctypes.byref(lo), ctypes.byref(cnt)))
     return int(lo.value), int(lo.value + cnt.value)
 
 
-class Comm:
+class Comm(_Handle):
     """A communicator of the C ABI (cb_comm, lsmt_amd/csrc/comm.cpp): the
     exchange a Rust ``Database::get`` would call over ``extern "C"``
     (INTEGRATION.md), driven here from Python. One process per GPU, ONE
@@ -71,30 +76,23 @@ class Comm:
     `world` ranks in this process (drive each from its own thread);
     ``Comm.host(rank, world, device, allgather)`` moves the bytes with a
     Python all-gather of host buffers."""
+    _destroy = "cb_comm_destroy"
 
     def __init__(self, rank: int, world: int, device: int, uid: bytes):
-        import ctypes
-
-        from . import _lib
         if len(uid) != _lib.COMM_ID_BYTES:
             raise ValueError("the communicator id is 128 bytes")
-        self._L = _lib.load()
         self._h = ctypes.c_void_p()
         buf = (ctypes.c_uint8 * len(uid)).from_buffer_copy(uid)
-        _lib.check(self._L.cb_comm_init(rank, world, ctypes.addressof(buf), device, ctypes.byref(self._h)))
+        _lib.check(_L().cb_comm_init(rank, world, ctypes.addressof(buf), device, ctypes.byref(self._h)))
         self.rank, self.world, self.device = rank, world, device
         self._keep = None
 
     @classmethod
     def _adopt(cls, handle: int, keep=None) -> "Comm":
-        import ctypes
-
-        from . import _lib
         c = cls.__new__(cls)
-        c._L = _lib.load()
         c._h = ctypes.c_void_p(handle)
         r, w, d = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-        _lib.check(c._L.cb_comm_info(c._h, ctypes.byref(r), ctypes.byref(w), ctypes.byref(d)))
+        _lib.check(_L().cb_comm_info(c._h, ctypes.byref(r), ctypes.byref(w), ctypes.byref(d)))
         c.rank, c.world, c.device = r.value, w.value, d.value
         c._keep = keep
         return c
@@ -104,11 +102,8 @@ class Comm:
         """`world` ranks in this process on `device` (cb_comm_init_loopback).
         Rank r's collectives must run on a thread of its own, concurrently
         with the other ranks' (each call returns when every rank made it)."""
-        import ctypes
-
-        from . import _lib
         arr = (ctypes.c_void_p * world)()
-        _lib.check(_lib.load().cb_comm_init_loopback(world, device, arr))
+        _lib.check(_L().cb_comm_init_loopback(world, device, arr))
         return [cls._adopt(arr[r]) for r in range(world)]
 
     @classmethod
@@ -116,11 +111,6 @@ class Comm:
         """A communicator whose bytes move through `allgather(send: bytes-like
         numpy uint8 array, recv: numpy uint8 array of world * len(send))`, a
         host-side all-gather the caller provides (cb_comm_init_host)."""
-        import ctypes
-
-        import numpy as np
-
-        from . import _lib
 
         def cb(user, send, recv, nbytes):
             try:
@@ -132,22 +122,18 @@ class Comm:
                 allgather(s, r)
                 return 0
             except Exception:  # reported to the library as a failed transport
-                import traceback
                 traceback.print_exc()
                 return 1
 
         fn = _lib.HOST_ALLGATHER_FN(cb)
         h = ctypes.c_void_p()
-        _lib.check(_lib.load().cb_comm_init_host(rank, world, device, fn, None, ctypes.byref(h)))
+        _lib.check(_L().cb_comm_init_host(rank, world, device, fn, None, ctypes.byref(h)))
         return cls._adopt(h.value, keep=fn)
 
     @staticmethod
     def unique_id() -> bytes:
-        import ctypes
-
-        from . import _lib
         buf = (ctypes.c_uint8 * _lib.COMM_ID_BYTES)()
-        _lib.check(_lib.load().cb_comm_unique_id(ctypes.addressof(buf)))
+        _lib.check(_L().cb_comm_unique_id(ctypes.addressof(buf)))
         return bytes(buf)
 
     @classmethod
@@ -162,20 +148,10 @@ class Comm:
         """cb_comm_abort: end the communicator from any thread (a watchdog),
         also while another thread is blocked in one of its collectives.
         Returns the C status (0 on success)."""
-        if getattr(self, "_h", None) is None or not self._h.value:
+        h = getattr(self, "_h", None)
+        if not h or not h.value:
             return 0
-        return int(self._L.cb_comm_abort(self._h))
-
-    def close(self) -> None:
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._L.cb_comm_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return int(_L().cb_comm_abort(h))
 
     def allgather(self, local_hits, n_total: int, out, sparse: bool = False, cap: int = 0, ok=None,
                   stream=None) -> bool:
@@ -186,10 +162,6 @@ class Comm:
         the host and the batch redone densely, with ok (an int32 device tensor
         holding 1) it is reported there instead. Returns whether the map came
         from the packs."""
-        import ctypes
-
-        from . import _lib
-        from .bloom import _ptr_of, _stream
         rows, words = local_hits.shape
         if tuple(out.shape) != (n_total, words):
             raise ValueError("out must be [n_total][words]")
@@ -197,7 +169,7 @@ class Comm:
         fp, k2 = _ptr_of(out)
         op, k3 = _ptr_of(ok)
         used = ctypes.c_int(0)
-        _lib.check(self._L.cb_hits_allgather(self._h, lp, rows, words, n_total, fp,
+        _lib.check(_L().cb_hits_allgather(self._h, lp, rows, words, n_total, fp,
                                              _lib.XCHG_SPARSE if sparse else _lib.XCHG_DENSE, cap, op,
                                              ctypes.byref(used), _stream(stream)))
         return bool(used.value)
@@ -209,17 +181,13 @@ class Comm:
         local_out [used][ceil(n/64)] and out [n_total][ceil(n/64)] int64
         device tensors. In sparse mode the probe kernel writes the pack
         itself. Returns whether the map came from the packs."""
-        import ctypes
-
-        from . import _lib
-        from .bloom import _ptr_of, _stream
         n = int(keys.shape[0])
         kp, k1 = _ptr_of(keys)
         lp, k2 = _ptr_of(local_out)
         fp, k3 = _ptr_of(out)
         op, k4 = _ptr_of(ok)
         used = ctypes.c_int(0)
-        _lib.check(self._L.cb_set_probe_allgather_fixed(
+        _lib.check(_L().cb_set_probe_allgather_fixed(
             self._h, fset._h, kp, int(keys.shape[1]), n, int(bool(gated)), lp, n_total, fp,
             _lib.XCHG_SPARSE if sparse else _lib.XCHG_DENSE, cap, op, ctypes.byref(used), _stream(stream)))
         return bool(used.value)

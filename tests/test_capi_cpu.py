@@ -89,27 +89,74 @@ def test_meta_encode_rejects_non_utf8_like_rust_strings():
 
 
 def test_table_handle_array_is_reused_only_for_the_same_open_tables():
-    # get_many's C array of table handles (lsmt_amd.bloom._table_array) is
+    # get_many's C array of table handles (lsmt_amd.get._table_array) is
     # kept per sequence while it names the same handle objects; a closed table
     # (Table.close() replaces its handle object), a replaced or reordered
     # table, or another sequence gets a fresh array with the current handles
-    from lsmt_amd import bloom
+    from lsmt_amd.get import _table_array
 
     class T:
         def __init__(self, v):
             self._h = ctypes.c_void_p(v)
 
     ts = [T(0x1000 + 64 * i) for i in range(300)]
-    a = bloom._table_array(ts)
-    assert bloom._table_array(ts) is a
+    a = _table_array(ts)
+    assert _table_array(ts) is a
     assert [a[i] for i in range(300)] == [0x1000 + 64 * i for i in range(300)]
     ts[7]._h = ctypes.c_void_p()  # closed
-    b = bloom._table_array(ts)
+    b = _table_array(ts)
     assert b is not a and b[7] is None
     ts[3], ts[4] = ts[4], ts[3]
-    c = bloom._table_array(ts)
+    c = _table_array(ts)
     assert c is not b and (c[3], c[4]) == (0x1000 + 64 * 4, 0x1000 + 64 * 3)
     rev = ts[::-1]
-    d = bloom._table_array(rev)
-    assert d[0] == 0x1000 + 64 * 299 and bloom._table_array(ts) is c
-    assert len(bloom._table_array([])) == 1  # the C ABI never reads it (nt = 0)
+    d = _table_array(rev)
+    assert d[0] == 0x1000 + 64 * 299 and _table_array(ts) is c
+    assert len(_table_array([])) == 1  # the C ABI never reads it (nt = 0)
+
+
+def test_base_handle_class_closes_once_and_replaces_the_handle_object():
+    from lsmt_amd._ffi import _Handle
+    freed = []
+
+    class H(_Handle):
+        def __init__(self, v):
+            self._h = ctypes.c_void_p(v)
+
+        def _free(self, h):
+            freed.append(h)
+
+    x = H(0x5000)
+    live = x._h
+    x.close()
+    assert len(freed) == 1 and freed[0] is live and live.value == 0x5000
+    assert x._h is not live and x._h.value is None
+    null = x._h
+    x.close()
+    assert len(freed) == 1 and x._h is null
+    H.__new__(H).close()  # the constructor raised before _h existed
+    assert len(freed) == 1
+
+    class Bad(H):
+        def _free(self, h):
+            raise RuntimeError("destroy failed")
+
+    bad = Bad(0x6000)
+    bad.__del__()  # swallowed; the handle stays, since destroy did not succeed
+    assert bad._h.value == 0x6000
+
+
+def test_ragged_packing_equals_the_obvious_loop():
+    from lsmt_amd._ffi import _pack
+    cases = [[], [b""], [b"ab", b"", b"", b"cde", b"", b"f"], [b"x", bytes(range(256)) * 274, b"yz"]]
+    assert len(cases[3][1]) > 70_000
+    for parts in cases:
+        data, off = _pack(parts)
+        want, at = [0], 0
+        for p in parts:
+            at += len(p)
+            want.append(at)
+        assert data == b"".join(parts)
+        assert off.dtype == np.uint64 and off.shape == (len(parts) + 1,)
+        assert off.tolist() == want and int(off[-1]) == len(data)
+    assert int(_pack(cases[3])[1][2]) > 0xFFFF

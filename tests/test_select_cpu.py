@@ -85,7 +85,7 @@ def test_surface():
     assert m, "no cb_select"
     fields = [f.split()[-1].lstrip("*") for f in m.group(1).split(";") if f.strip()]
     assert fields == ["cols", "col_off", "part", "cast", "nc"]
-    from lsmt_amd.bloom import _CbSelect
+    from lsmt_amd.rows import _CbSelect
     assert [n for n, _ in _CbSelect._fields_] == fields
     assert ctypes.sizeof(_CbSelect) == 40
     assert [getattr(_CbSelect, f).offset for f in fields] == [0, 8, 16, 24, 32]

@@ -264,7 +264,7 @@ def test_get_many_decode_scan_boundary(gpu):
 
 def test_get_many_same_list_mutated_between_calls(gpu):
     """One table list passed batch after batch while it changes in place
-    (get_many keeps its handle array per list object, lsmt_amd.bloom.
+    (get_many keeps its handle array per list object, lsmt_amd.get.
     _table_array): a table replaced by a new one, the list reordered, a table
     closed and its slot refilled, the list grown. Every call equals the
     oracle over the list as it is at that call."""

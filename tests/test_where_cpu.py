@@ -73,7 +73,7 @@ def test_surface():
     assert m, "no cb_where"
     fields = [f.split()[-1].lstrip("*") for f in m.group(1).split(";") if f.strip()]
     assert fields == ["cols", "col_off", "vals", "val_off", "part", "nc"]
-    from lsmt_amd.bloom import _CbWhere
+    from lsmt_amd.rows import _CbWhere
     assert [n for n, _ in _CbWhere._fields_] == fields
     assert ctypes.sizeof(_CbWhere) == 48 and _CbWhere.nc.offset == 40
     # the new section follows the last-write-wins one and cites the reference lines the rule comes from

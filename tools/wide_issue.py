@@ -18,7 +18,7 @@ import torch  # noqa: E402
 
 import lsmt_amd  # noqa: E402
 from lsmt_amd import _lib, workload  # noqa: E402
-from lsmt_amd.bloom import _ptr_of  # noqa: E402
+from lsmt_amd._ffi import _ptr_of  # noqa: E402
 
 
 def main():
