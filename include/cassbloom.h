@@ -705,6 +705,107 @@ int cb_rows_info(const void* rows, uint64_t* count, uint64_t* with_text, uint64_
 int cb_rows_text(const void* rows, uint8_t* text, uint64_t* row_at, uint64_t* row_len, uint8_t* flags);
 /* Retires the result's memory through the block pool, as cb_scan_destroy. */
 int cb_rows_destroy(void* rows);
+/* ---- the token ring: which node holds which row ---------------------------------
+ * The fold above treats tables as replicas; this is the rule that says which
+ * node is a replica of which row. The reference places rows with a murmur3
+ * token ring: Cluster::new (src/cluster.rs:46-54) inserts, for each node in
+ * order and each v in 0 .. max(vnodes, 1), the position
+ * (murmur3_32("{node}-{v}"), node) into a BTreeMap by token, a later insert
+ * replacing an earlier one of the same token, and replicas_for
+ * (src/cluster.rs:102-123) walks the positions with token >= t ascending, then
+ * the whole ring from its first position, collecting the nodes not collected
+ * yet until it holds rf = max(rf, 1) of them. It is asked about the partition
+ * keys that SqlEngine::partition_keys cuts out of a statement
+ * (src/query.rs:448-528, 697-713, 734-760). The rule's full text is
+ * lsmt_amd/csrc/ring.hpp's; its hash is a restatement of MurmurHash3 x86_32
+ * (seed 0) that was not run against the reference.
+ * TOKEN of a byte string: MurmurHash3 x86_32, seed 0; bytes are unsigned.
+ * PARTITION KEY of a stored key: rest = the key without its first
+ * min(skip, len) bytes; with npk == 0, or when rest has at most npk
+ * `|`-separated parts, all of rest; else rest up to, not including, its
+ * npk-th `|` (the first npk parts joined again).
+ * REPLICAS of token t: an ordered list, the primary first, of width =
+ * min(rf, nodes that hold a position) node indices for every t. Lists are rf
+ * wide, -1 past width. Nodes are 0 .. nnodes - 1 in the caller's order
+ * (Cluster::new pushes the own node last).
+ * A ring handle (`ring` below is a cb_ring, spelled void* as cb_scan is) is
+ * immutable. Creating and asking it on the host touches no device; a device's
+ * copy (the sorted tokens and each position's replica list) is made on that
+ * device's first route or compaction. */
+/* Cluster::new's ring: node i's name is names[name_off[i] .. name_off[i+1]).
+ * CB_EINVAL, *out = NULL: a NULL argument; nnodes == 0 or > 4096; vnodes >
+ * 4096; rf > 16; more than 2^20 positions; offsets that decrease; an empty
+ * name; two equal names (replicas_for compares names: deduplicate first).
+ * vnodes == 0 and rf == 0 act as 1. */
+int cb_ring_create(const uint8_t* names, const uint64_t* name_off /* nnodes+1 */, uint32_t nnodes,
+                   uint32_t vnodes, uint32_t rf, void** out /* cb_ring */);
+/* The ring of explicit (tokens[i], owners[i]) pairs, inserted in order, a
+ * later pair replacing an earlier one of the same token: for callers with
+ * tokens of their own. CB_EINVAL as above, and for npos == 0 or > 2^20 and an
+ * owner >= nnodes. */
+int cb_ring_create_tokens(const uint32_t* tokens, const uint32_t* owners, uint64_t npos, uint32_t nnodes,
+                          uint32_t rf, void** out /* cb_ring */);
+/* Every output nullable. positions: the distinct tokens; width: as above. */
+int cb_ring_info(const void* ring, uint32_t* nnodes, uint32_t* rf, uint64_t* positions, uint32_t* width);
+/* The positions ascending by token, `positions` entries each (either nullable). */
+int cb_ring_tokens(const void* ring, uint32_t* tokens, uint32_t* owners);
+/* replicas_for of one key on the host: *token (nullable) the partition key's
+ * token, replicas (nullable) its rf-wide list. */
+int cb_ring_replicas(const void* ring, const uint8_t* key, uint64_t len, uint32_t skip, uint32_t npk,
+                     uint32_t* token /* nullable */, int32_t* replicas /* rf, nullable */);
+/* Retires the device copies through the block pool, like every other handle:
+ * no device-wide synchronise. */
+int cb_ring_destroy(void* ring);
+/* The batched replicas_for on `device`: tokens[i] and replicas[i * rf ..] of
+ * key i, for n keys with one skip and npk. Residency and waiting follow
+ * cb_probe_*: device buffers are used in place and the call is asynchronous on
+ * `stream`; host buffers are staged and the call waits. n == 0 writes nothing;
+ * both outputs NULL is CB_EINVAL. */
+int cb_ring_route_fixed(const void* ring, const uint8_t* keys, uint32_t key_len, uint64_t n, uint32_t skip,
+                        uint32_t npk, int device, uint32_t* tokens /* n, nullable */,
+                        int32_t* replicas /* n*rf, nullable */, void* stream);
+int cb_ring_route_var(const void* ring, const uint8_t* bytes, const uint64_t* offsets /* n+1 */, uint64_t n,
+                      uint32_t skip, uint32_t npk, int device, uint32_t* tokens /* n, nullable */,
+                      int32_t* replicas /* n*rf, nullable */, void* stream);
+/* The same over the keys of a result of any cb_tables_scan* call, skip and npk
+ * per range of the result (cb_scan_ranges), as cb_scan_match takes its skip.
+ * Synchronous; outputs to host or device memory, as cb_scan_which copies.
+ * Nothing is written for an empty result. */
+int cb_scan_route(const void* r /* cb_scan */, const void* ring, const uint32_t* skip /* per range, nullable */,
+                  const uint32_t* npk /* per range, nullable */, uint32_t* tokens /* count, nullable */,
+                  int32_t* replicas /* count*rf, nullable */);
+/* Which keys are partitioned, and how: a key that starts with prefix r has
+ * skip = len(prefix r) and npk[r]. The prefixes ascend and none starts with
+ * another (cb_tables_scan_prefixes' ordering rule); at most 256 of them and
+ * 4096 bytes together. np == 0 is legal. */
+typedef struct cb_key_rules {   /* host memory */
+  const uint8_t* prefixes; const uint64_t* prefix_off;   /* np+1, non-decreasing */
+  const uint32_t* npk;                                   /* np */
+  uint32_t np;
+} cb_key_rules;
+/* The compaction a node runs after the ring changed, or to cut what a joining
+ * node must receive (Cassandra's cleanup; the reference never does it, as it
+ * never compacts): the file is SsTable::create of { (k, v) in E : owned(k) }.
+ * E is the entries of cb_tables_compact (lww == 0) or cb_tables_compact_lww
+ * (lww != 0), drop_dead as in cb_tables_compact_live / _lww, and with it THE
+ * CALLER'S RULE: dropping dead winners is correct only when
+ * no table or replica of the store stays outside the list.
+ * owned(k): a key under prefix r
+ * of the rules is owned when `node` is among the first `ranks` entries of its
+ * replica list (ranks == 0: all rf); a key under no prefix is owned by every
+ * node, as the reference broadcasts its catalog writes to the whole ring
+ * (src/cluster.rs:277-286, 313-314), so `_tables:` and `_schema:` rows stay
+ * everywhere. Ownership depends on the key alone, so the filter runs behind
+ * the merge's select: two more launches than the base entry. No owned entry
+ * gives the empty file. Bloom filter, line index, zone bounds, waits and the
+ * table-list refusals are cb_tables_compact's. Its own arguments are checked
+ * before the table list, outputs cleared: a NULL table_out, ring or rules;
+ * node >= nnodes; ranks > 16; rules that break the above; m_bits == 0 with a
+ * filter asked for (CB_EZEROM). `rules` is a const cb_key_rules*. */
+int cb_tables_compact_ring(const cb_table* const* tables, uint32_t nt, uint64_t m_bits, const void* ring,
+                           uint32_t node, uint32_t ranks, const void* rules /* cb_key_rules */, int lww,
+                           int drop_dead, void* stream, cb_table** table_out,
+                           cb_filter** bloom_out /* nullable */);
 /* Finalise a table from cb_sstable_create*: wait for its work, take its
  * results; returns its deferred error, if any. Idempotent, thread-safe. */
 int cb_table_wait(const cb_table* t);

@@ -62,6 +62,12 @@ class LogStats(ctypes.Structure):
         return "LogStats(%s)" % ", ".join("%s=%d" % (n, getattr(self, n)) for n, _ in self._fields_)
 
 
+class KeyRules(ctypes.Structure):
+    """struct cb_key_rules (include/cassbloom.h)."""
+    _fields_ = [("prefixes", ctypes.c_void_p), ("prefix_off", ctypes.c_void_p), ("npk", ctypes.c_void_p),
+                ("np", ctypes.c_uint32)]
+
+
 class MetaInfo(ctypes.Structure):
     """struct cb_meta_info (include/cassbloom.h)."""
     _fields_ = [("has_bloom", ctypes.c_int), ("has_zone", ctypes.c_int), ("zone", ZoneBounds)]
@@ -183,6 +189,16 @@ def load():
         "cb_rows_info": ([P, pu64, pu64, pu64], i32),
         "cb_rows_text": ([P, u8p, P, P, u8p], i32),
         "cb_rows_destroy": ([P], i32),
+        "cb_ring_create": ([u8p, P, u32, u32, u32, pp], i32),
+        "cb_ring_create_tokens": ([P, P, u64, u32, u32, pp], i32),
+        "cb_ring_info": ([P, ctypes.POINTER(u32), ctypes.POINTER(u32), pu64, ctypes.POINTER(u32)], i32),
+        "cb_ring_tokens": ([P, P, P], i32),
+        "cb_ring_replicas": ([P, u8p, u64, u32, u32, ctypes.POINTER(u32), P], i32),
+        "cb_ring_destroy": ([P], i32),
+        "cb_ring_route_fixed": ([P, u8p, u32, u64, u32, u32, i32, P, P, P], i32),
+        "cb_ring_route_var": ([P, u8p, P, u64, u32, u32, i32, P, P, P], i32),
+        "cb_scan_route": ([P, P, P, P, P, P], i32),
+        "cb_tables_compact_ring": ([P, u32, u64, P, u32, u32, P, i32, i32, P, pp, pp], i32),
         "cb_scan_ranges": ([P, pu64, P], i32),
         "cb_key_prefix_end": ([u8p, u64, u8p, pu64, ctypes.POINTER(i32)], i32),
         "cb_scan_info": ([P, pu64, pu64, pu64, ctypes.POINTER(i32)], i32),

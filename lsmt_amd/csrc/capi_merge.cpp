@@ -6,7 +6,9 @@
 // greatest timestamp (rowts.hpp) in place of its newest one. The merge's
 // other user, the scans and counts, is capi_scan.cpp, and the log replay
 // (capi_replay.cpp) runs it over its own gather and then takes compaction's
-// steps behind it; capi_merge.hpp declares what they need.
+// steps behind it, and the ring's compaction (capi_ring.cpp) is compact_tables
+// with a step of its own behind the select; capi_merge.hpp declares what they
+// need.
 //
 // Reference: src/sstable.rs:51-98 (the file a compaction writes),
 // src/lib.rs:125-146 (Database::get, whose answers it reproduces), src/cluster.rs:405-416,
@@ -180,20 +182,26 @@ int compact_sources(const cb_table* const* tables, uint32_t nt, std::vector<cb::
 
 // 2: the merge over the sources, staged into its scratch (one wait: the
 // source is pageable), up to the survivors' totals h (enqueue_merge's wait).
+// after (nullable): a step of the caller's between the select and the totals.
 int merge_sources(const std::vector<cb::CompactSrc>& srcs, uint64_t n, uint64_t kbound, MergeRule rule,
-                  TempBlock& tmp, Merge* mg, hipStream_t s, uint64_t (&h)[3]) {
+                  const AfterSelect* after, TempBlock& tmp, Merge* mg, hipStream_t s, uint64_t (&h)[3]) {
   const uint32_t nsrc = (uint32_t)srcs.size();
   if (int rc = merge_alloc(nsrc, n, kbound, rule.order, tmp, mg)) return rc;
   HIP_TRY(hipMemcpyAsync(mg->dsrc, srcs.data(), nsrc * sizeof(cb::CompactSrc), hipMemcpyHostToDevice, s));
   HIP_TRY(hipStreamSynchronize(s));  // the source is pageable
-  return enqueue_merge(*mg, mg->dsrc, nsrc, rule, s, h);
+  if (!after) return enqueue_merge(*mg, mg->dsrc, nsrc, rule, s, h);
+  if (int rc = enqueue_merge_select(*mg, mg->dsrc, nsrc, rule, s)) return rc;
+  if (int rc = (*after)(*mg, s)) return rc;
+  return merge_totals(*mg, s, h);
 }
 
-// The live-row and LWW compactions check their own arguments before they look
-// at the table list (compact_tables looks at the list first): a filter of no
-// bits is refused here, the outputs cleared. Without both outputs the refusal
-// is compact_tables' own.
-int zero_m_before_tables(uint64_t m_bits, cb_table** table_out, cb_filter** bloom_out) {
+}  // namespace
+
+// The live-row, LWW and ring compactions check their own arguments before they
+// look at the table list (compact_tables looks at the list first): a filter of
+// no bits is refused here, the outputs cleared. Without both outputs the
+// refusal is compact_tables' own.
+int cbx::zero_m_before_tables(uint64_t m_bits, cb_table** table_out, cb_filter** bloom_out) {
   if (!table_out || !bloom_out || m_bits != 0) return CB_OK;
   *table_out = nullptr;
   *bloom_out = nullptr;
@@ -202,9 +210,10 @@ int zero_m_before_tables(uint64_t m_bits, cb_table** table_out, cb_filter** bloo
 
 // cb_tables_compact and, by their rules, cb_tables_compact_live and
 // cb_tables_compact_lww: the same steps over the same merge, whose select
-// alone knows the difference.
-int compact_tables(const cb_table* const* tables, uint32_t nt, uint64_t m_bits, MergeRule rule, void* stream,
-                   cb_table** table_out, cb_filter** bloom_out) {
+// alone knows the difference. cb_tables_compact_ring (capi_ring.cpp) takes
+// them too, with its ownership filter as the step after the select.
+int cbx::compact_tables(const cb_table* const* tables, uint32_t nt, uint64_t m_bits, MergeRule rule,
+                        const AfterSelect* after, void* stream, cb_table** table_out, cb_filter** bloom_out) {
   if (!table_out) return fail(CB_EINVAL, "null argument");
   *table_out = nullptr;
   if (bloom_out) *bloom_out = nullptr;
@@ -232,7 +241,7 @@ int compact_tables(const cb_table* const* tables, uint32_t nt, uint64_t m_bits, 
   if (n) {
     Merge mg;
     KeptKeys k;
-    if ((rc = merge_sources(srcs, n, kbound, rule, tmp, &mg, s, h))) return rc;
+    if ((rc = merge_sources(srcs, n, kbound, rule, after, tmp, &mg, s, h))) return rc;
     if ((rc = format_survivors(t.get(), mg, h, keys, &k, s))) return rc;
     if (h[0] && f) {
       // 4: BloomFilter::new(m) + insert per kept key (src/sstable.rs:59-63)
@@ -248,8 +257,6 @@ int compact_tables(const cb_table* const* tables, uint32_t nt, uint64_t m_bits, 
   return CB_OK;
 }
 
-}  // namespace
-
 extern "C" {
 
 // Newest-wins merge (compact.hpp). Every temporary is carved from pool blocks
@@ -260,7 +267,7 @@ extern "C" {
 // zone bounds are host results).
 int cb_tables_compact(const cb_table* const* tables, uint32_t nt, uint64_t m_bits, void* stream,
                       cb_table** table_out, cb_filter** bloom_out) {
-  return compact_tables(tables, nt, m_bits, kNewest, stream, table_out, bloom_out);
+  return compact_tables(tables, nt, m_bits, kNewest, nullptr, stream, table_out, bloom_out);
 }
 
 // The same with the live-row select: tombstones shadow and are then dropped
@@ -271,7 +278,7 @@ int cb_tables_compact(const cb_table* const* tables, uint32_t nt, uint64_t m_bit
 int cb_tables_compact_live(const cb_table* const* tables, uint32_t nt, uint64_t m_bits, void* stream,
                            cb_table** table_out, cb_filter** bloom_out) {
   if (int rc = zero_m_before_tables(m_bits, table_out, bloom_out)) return rc;
-  return compact_tables(tables, nt, m_bits, kLive, stream, table_out, bloom_out);
+  return compact_tables(tables, nt, m_bits, kLive, nullptr, stream, table_out, bloom_out);
 }
 
 // The LWW entries: the live-row entries' argument order (their own arguments
@@ -280,7 +287,8 @@ int cb_tables_compact_live(const cb_table* const* tables, uint32_t nt, uint64_t 
 int cb_tables_compact_lww(const cb_table* const* tables, uint32_t nt, uint64_t m_bits, int drop_dead, void* stream,
                           cb_table** table_out, cb_filter** bloom_out) {
   if (int rc = zero_m_before_tables(m_bits, table_out, bloom_out)) return rc;
-  return compact_tables(tables, nt, m_bits, MergeRule{MergeOrder::lww, drop_dead != 0}, stream, table_out, bloom_out);
+  return compact_tables(tables, nt, m_bits, MergeRule{MergeOrder::lww, drop_dead != 0}, nullptr, stream, table_out,
+                        bloom_out);
 }
 
 }  // extern "C"

@@ -1,9 +1,12 @@
 // capi_merge.hpp — what the two users of the device merge share
 // (capi_merge.cpp: the merge itself, the table-list checks and compaction;
 // capi_scan.cpp: scans, counts and the scan result), capi_select.cpp, which
-// stages its selection the way they stage theirs, and capi_replay.cpp, whose
-// log replay is the merge over one unsorted input. Included only by them.
+// stages its selection the way they stage theirs, capi_replay.cpp, whose
+// log replay is the merge over one unsorted input, and capi_ring.cpp, whose
+// compaction is compaction with one step more. Included only by them.
 #pragma once
+#include <functional>
+
 #include "capi_table.hpp"
 #include "compact.hpp"
 
@@ -93,6 +96,18 @@ int format_survivors(cb_table* t, const Merge& mg, const uint64_t (&h)[3], TempB
 int finish_compacted(cb_table* t, const Merge& mg, const KeptKeys& k, const uint64_t (&h)[3], hipStream_t s);
 // A filter of no bits: BloomFilter::insert's `% 0` (src/bloom.rs:36).
 int zero_m_error();
+// That refusal made before the table list is looked at, the outputs cleared
+// (the live-row, LWW and ring compactions); CB_OK otherwise.
+int zero_m_before_tables(uint64_t m_bits, cb_table** table_out, cb_filter** bloom_out);
+// A step of the caller's between a merge's select and its totals, enqueued on
+// the merge's stream: it may only clear survivors (slen[p] = 0) and must leave
+// the tile sums right (compact.hpp launch_compact_tiles).
+using AfterSelect = std::function<int(const Merge&, hipStream_t)>;
+// Compaction: the table list checked, the sources merged under `rule` (after,
+// nullable, behind the select), the survivors formatted into a new table with
+// its Bloom filter (bloom_out nullable), line index and zone bounds.
+int compact_tables(const cb_table* const* tables, uint32_t nt, uint64_t m_bits, cb::MergeRule rule,
+                   const AfterSelect* after, void* stream, cb_table** table_out, cb_filter** bloom_out);
 
 // ---- host values on their way into a call's scratch block ----
 

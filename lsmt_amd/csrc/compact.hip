@@ -297,6 +297,12 @@ hipError_t launch_compact_select_lww(const SortKey* order, const CompactSide* si
     hipLaunchKernelGGL(k, dim3(blocks_for(n, kNT)), dim3(kNT), 0, s, order, side, ts, kb, ko, n, slen);
     if (hipError_t e = hipGetLastError()) return e;
   }
+  return launch_compact_tiles(order, side, slen, n, tcnt, tbytes, tkeys, s);
+}
+
+hipError_t launch_compact_tiles(const SortKey* order, const CompactSide* side, const uint64_t* slen, uint64_t n,
+                                uint64_t* tcnt, uint64_t* tbytes, uint64_t* tkeys, hipStream_t s) {
+  if (!n) return hipSuccess;
   ProfScope ps("k_compact_lww_tiles", s);
   hipLaunchKernelGGL(k_compact_lww_tiles, dim3(blocks_for(n, kNT)), dim3(kNT), 0, s, order, side, slen, n, tcnt,
                      tbytes, tkeys);

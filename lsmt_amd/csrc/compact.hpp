@@ -136,6 +136,11 @@ hipError_t launch_compact_select_lww(const SortKey* order, const CompactSide* si
                                      const uint8_t* kb, const uint64_t* ko, uint64_t n, bool drop_dead,
                                      uint64_t* slen, uint64_t* tcnt, uint64_t* tbytes, uint64_t* tkeys,
                                      hipStream_t s);
+// The LWW select's second launch alone: the tile sums of slen as it stands,
+// for a caller that has cleared survivors behind a select (the ring's
+// ownership filter, capi_ring.cpp).
+hipError_t launch_compact_tiles(const SortKey* order, const CompactSide* side, const uint64_t* slen, uint64_t n,
+                                uint64_t* tcnt, uint64_t* tbytes, uint64_t* tkeys, hipStream_t s);
 // From the scanned tile sums: the file (out: the survivors' lines `key \t
 // text \n` back to back), its line index without re-reading it (sstable.hpp
 // layout: survivor l is line l of nl; vdl carried over from the input's
