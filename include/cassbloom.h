@@ -1118,6 +1118,104 @@ int cb_log_replay(const uint8_t* log, uint64_t len, uint64_t m_bits, int device,
  * decoded length, 0 both otherwise. Host only, no device access. */
 int cb_log_line(const uint8_t* piece, uint64_t len, int* kind, uint64_t* key_len, uint64_t* value_len);
 
+/* ---- the coordinator's read merge: the replicas' replies folded on the device ---- */
+/* A winner's verdict (cb_fold_rows' flags, cb_reply_line's val_flags): its
+ * val is copied into the response byte for byte, it is a deleted row (an
+ * empty val) and left out, or the library does not decide it. */
+#define CB_FOLD_TEXT 1
+#define CB_FOLD_DEAD 2
+#define CB_FOLD_HOST 4
+/* What cb_replies_fold saw. After CB_EUTF8 bad_reply is the first reply in
+ * order with a piece that is not UTF-8 and bad_offset the offset in `bytes` of
+ * that reply's first such piece (every count but replies is then 0);
+ * UINT64_MAX both otherwise. */
+typedef struct {
+    uint64_t replies;    /* nr */
+    uint64_t lines;      /* lines that are not empty after the strip */
+    uint64_t entries;    /* of those with two TABs */
+    uint64_t others;     /* of those with fewer */
+    uint64_t keys;       /* distinct keys among the entries = winners */
+    uint64_t with_text;  /* winners whose val is in the response (CB_FOLD_TEXT) */
+    uint64_t dead;       /* winners with an empty val (CB_FOLD_DEAD) */
+    uint64_t host_rows;  /* winners the caller does again (CB_FOLD_HOST) */
+    uint64_t bytes;      /* the response's length */
+    uint64_t bad_reply;  /* UINT64_MAX, or the reply */
+    uint64_t bad_offset; /* UINT64_MAX, or the piece's offset in bytes */
+} cb_fold_stats;
+/* The last step of the reference's cluster read (Cluster::execute,
+ * src/cluster.rs:394-473, is_write false) over the replies of nr replicas, in
+ * the caller's order (the reference's is a HashSet's): what cb_scan_select /
+ * cb_rows_select write with CB_SELECT_META on every replica goes in, the
+ * response bytes the client gets come out. The rule is
+ * lsmt_amd/csrc/replyline.hpp's:
+ *  - a reply must be UTF-8 (the reference's from_utf8_lossy replacement is left
+ *    to the caller): the first reply in order with an invalid piece fails the
+ *    call with CB_EUTF8, *out is NULL and *stats names it;
+ *  - lines are str::lines() of each reply by itself: split at 0x0A, a piece a
+ *    newline ended loses one trailing 0x0D, the last piece of a reply without
+ *    a final newline keeps its 0x0D, replies are never joined, and a line that
+ *    is empty after the strip is ignored;
+ *  - a line with at least two TABs is an entry: key (it may be empty), the
+ *    timestamp's text, val (further TABs included). The timestamp is
+ *    str::parse::<u64>().unwrap_or(0): an optional single +, then ASCII digits
+ *    only, at most 2^64 - 1; anything else is 0. Any other non-empty line is an
+ *    "other";
+ *  - per key the entry with the greatest timestamp wins, of equal ones the
+ *    first in (reply, line) order;
+ *  - the winners are walked ascending by key bytes. An empty val is a deleted
+ *    row and left out (CB_FOLD_DEAD). A val in canonical form (an object of
+ *    strings without whitespace, its names strictly ascending, every string as
+ *    serde_json writes it; {} included) is copied byte for byte
+ *    (CB_FOLD_TEXT): serde_json's parse and re-serialisation is the identity
+ *    for it. Every other val is CB_FOLD_HOST: it may be invalid JSON, which
+ *    the reference drops, or JSON that re-serialises differently; its text is
+ *    left out of the response and the caller does that row again from its
+ *    span (cb_fold_rows). Every row cb_scan_select writes is canonical, so a
+ *    cluster of this library's nodes sees host_rows == 0;
+ *  - the response: with at least one entry, [ + the CB_FOLD_TEXT texts joined
+ *    by , + ]; with no entry but others, the bytewise least other line,
+ *    verbatim (a forwarded COUNT(*) reply travels so); else [].
+ * Where the others decide the response the call reads the pieces' verdicts
+ * (and, for device input, the staged replies) back and takes the least on the
+ * host: in everything the reference sends there they are one short line per
+ * reply. A failed replica is simply not in the list.
+ * bytes: host or device memory; reply r is bytes[off[r] .. off[r + 1]), off
+ * (host memory) holds nr + 1 offsets. device == -1 folds on the host by the
+ * same rule: bytes must then be host memory, no device is touched and the
+ * result is the same kind of object. CB_EINVAL, *out NULL: out NULL; off NULL
+ * with nr > 0; bytes NULL with a non-zero total; offsets that decrease;
+ * nr > 4096; a piece of 4 GiB or more; 2^32 or more entries (the last two can
+ * only occur with 4 GiB of replies or more; below that no device work is
+ * needed to rule them out, above it the device finds them). nr == 0 or no
+ * bytes at all gives a valid object whose text is []. The call waits for its
+ * own stream wherever a size depends on the data (the pieces' count, the
+ * entries' counts, the winners' totals, and at the end), never for the device,
+ * and retires its blocks through the pool. The result is complete when the
+ * call returns and does not depend on bytes afterwards. */
+int cb_replies_fold(const uint8_t* bytes, const uint64_t* off, uint32_t nr, int device, void* stream,
+                    void** out /* cb_fold */, void* stats /* cb_fold_stats, nullable */);
+int cb_fold_info(const void* fold, void* stats /* cb_fold_stats */);
+/* The response (stats.bytes bytes) into host or device memory. */
+int cb_fold_text(const void* fold, uint8_t* text);
+/* The winners in key order, stats.keys entries each, every argument nullable,
+ * into host or device memory: where the key and the val lie in the caller's
+ * bytes and how long they are, the parsed timestamp, the reply the winner came
+ * from and its CB_FOLD_* flag. The object keeps no copy of the replies. */
+int cb_fold_rows(const void* fold, uint64_t* key_at, uint64_t* key_len, uint64_t* ts, uint64_t* val_at,
+                 uint64_t* val_len, uint32_t* reply, uint8_t* flags);
+/* Where the least other line lies in the caller's bytes, when the others
+ * decided the response (no entry at all); *at = UINT64_MAX, *len = 0 otherwise. */
+int cb_fold_other(const void* fold, uint64_t* at, uint64_t* len);
+int cb_fold_destroy(void* fold);
+/* The verdict of one piece of a reply (no 0x0A inside: CB_EINVAL) by the same
+ * rule; terminated says whether a newline of its reply followed it. *kind = 0
+ * ignored (empty after the strip), 1 an entry, 2 an other, or CB_EUTF8; for an
+ * entry *key_len, *ts, *val_at (the val's offset in the piece), *val_len and
+ * *val_flags (its CB_FOLD_* verdict) are set, 0 all otherwise. Every output
+ * but kind is nullable. Host only, no device access. */
+int cb_reply_line(const uint8_t* piece, uint64_t len, int terminated, int* kind, uint64_t* key_len, uint64_t* ts,
+                  uint64_t* val_at, uint64_t* val_len, uint8_t* val_flags);
+
 /* ---- tuning / introspection (bench + tests) ---- */
 /* Path selection: 0 = auto, 1 = force direct (per-key atomics / gathers),
  * 2 = force tiled (LDS-staged filter tiles). Process-wide. */

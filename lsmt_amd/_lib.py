@@ -62,6 +62,15 @@ class LogStats(ctypes.Structure):
         return "LogStats(%s)" % ", ".join("%s=%d" % (n, getattr(self, n)) for n, _ in self._fields_)
 
 
+class FoldStats(ctypes.Structure):
+    """struct cb_fold_stats (include/cassbloom.h)."""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("replies", "lines", "entries", "others", "keys", "with_text", "dead",
+                                                "host_rows", "bytes", "bad_reply", "bad_offset")]
+
+    def __repr__(self):
+        return "FoldStats(%s)" % ", ".join("%s=%d" % (n, getattr(self, n)) for n, _ in self._fields_)
+
+
 class KeyRules(ctypes.Structure):
     """struct cb_key_rules (include/cassbloom.h)."""
     _fields_ = [("prefixes", ctypes.c_void_p), ("prefix_off", ctypes.c_void_p), ("npk", ctypes.c_void_p),
@@ -211,6 +220,14 @@ def load():
         "cb_table_rebuild": ([P, u64, P, pp, pu64, pu64], i32),
         "cb_log_replay": ([u8p, u64, u64, i32, P, pp, pp, P], i32),
         "cb_log_line": ([u8p, u64, ctypes.POINTER(i32), pu64, pu64], i32),
+        "cb_replies_fold": ([u8p, P, u32, i32, P, pp, P], i32),
+        "cb_fold_info": ([P, P], i32),
+        "cb_fold_text": ([P, u8p], i32),
+        "cb_fold_rows": ([P, P, P, P, P, P, P, P], i32),
+        "cb_fold_other": ([P, pu64, pu64], i32),
+        "cb_fold_destroy": ([P], i32),
+        "cb_reply_line": ([u8p, u64, i32, ctypes.POINTER(i32), pu64, pu64, pu64, pu64, ctypes.POINTER(ctypes.c_uint8)],
+                          i32),
         "cb_table_well_formed": ([P, ctypes.POINTER(i32)], i32),
         "cb_table_force_exact": ([i32], i32),
         "cb_table_bucket_limit": ([u64], i32),

@@ -64,4 +64,11 @@ constexpr bool lww_beats(uint64_t ts_a, uint64_t idx_a, uint64_t ts_b, uint64_t 
   return ts_a != ts_b ? ts_a > ts_b : idx_a < idx_b;
 }
 
+// The same fold taken one row at a time, as src/cluster.rs:405-416 runs it:
+// whether the row met now (ts, at place idx) replaces the row kept so far.
+// The host fold of the replicas' replies (replyfold.hpp) asks here.
+constexpr bool lww_replaces(uint64_t kept_ts, uint64_t kept_idx, uint64_t ts, uint64_t idx) {
+  return lww_beats(ts, idx, kept_ts, kept_idx);
+}
+
 }  // namespace cb
