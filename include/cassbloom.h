@@ -1216,6 +1216,104 @@ int cb_fold_destroy(void* fold);
 int cb_reply_line(const uint8_t* piece, uint64_t len, int terminated, int* kind, uint64_t* key_len, uint64_t* ts,
                   uint64_t* val_at, uint64_t* val_len, uint8_t* val_flags);
 
+/* ---- INSERT, UPDATE, DELETE: rows written to keys, values and log records on the device ---- */
+/* The first step of the reference's write path for a batch of n rows of one
+ * prepared statement: exec_insert + build_row (src/query.rs:162-198, 716-731),
+ * exec_update (src/query.rs:201-237) or exec_delete (src/query.rs:240-261),
+ * encode_row (src/schema.rs:37-39), then insert_ns_ts / insert_ts /
+ * insert_internal (src/lib.rs:96-116, 154-157). The rule is
+ * lsmt_amd/csrc/rowwrite.hpp's; the SQL parser stays with the caller.
+ * The statement (cb_write, host memory): the namespace ns; nk <= 16 key
+ * columns in the caller's order (INSERT: the statement's column order, which
+ * build_row pushes; UPDATE and DELETE: the schema's key_columns()); nc <= 16
+ * payload column names, strictly ascending bytewise, at most 4096 bytes
+ * (cb_select's rules); set[c] = 1 the statement gives column c's value, 0 the
+ * old row's is kept; op: CB_WRITE_INSERT (every set[c] is 1, no old rows),
+ * CB_WRITE_UPDATE, CB_WRITE_DELETE (nc == 0, no old rows).
+ * Cells: with w = nk + the number of set columns, cell (i, j) is
+ * cells[cell_off[i * w + j] .. cell_off[i * w + j + 1]); a row's key cells come
+ * first, then the set columns' in name order. Per row:
+ *  - key: ns ':' and the key cells joined by '|' (`ns:` with nk == 0);
+ *  - old map (UPDATE, old_which[i] >= 0): split_ts of old value i, its payload
+ *    read as cb_rows_select reads one; an error anywhere or an empty payload (a
+ *    tombstone) gives the empty map, decode_row's unwrap_or_default; of a
+ *    duplicated name the last pair wins;
+ *  - payload: none for DELETE; else {"name":"value",...} over the columns
+ *    with a value in name order, without spaces, every string as serde_json
+ *    writes it: a set column has its cell ("" for an empty one), a kept column
+ *    the old map's value, a kept column without one is left out; {} is a live
+ *    row, unlike DELETE's empty payload;
+ *  - value: the row's timestamp (ts[i], or ts_all when ts is NULL) as 8
+ *    big-endian bytes, then the payload;
+ *  - log record: key \t STANDARD.encode(value) \n, what insert_internal
+ *    appends and cb_log_replay reads;
+ *  - flags: CB_WRITTEN_HOST the old payload is a valid map with a name outside
+ *    the nc columns (names are not sorted per row on the device: the row is
+ *    the caller's, as CB_ROW_EXTRA's and CB_FOLD_HOST's are; its key is
+ *    written, its value and record have length 0); CB_WRITTEN_BADOLD the old
+ *    payload was no valid map and counted as empty (a tombstone is not
+ *    flagged); CB_WRITTEN_KEYCTL the key holds \t or \n, so its record does not
+ *    replay to the same key (the row is written all the same).
+ * Cell bytes are the caller's Rust Strings: UTF-8 is not checked.
+ * cells, cell_off and ts: host or device memory (host inputs are staged; a
+ * host cells with device offsets costs one read-back of the last offset). The
+ * old arrays are device memory, as an enqueue-only cb_*get_many leaves them.
+ * The work is enqueued on `stream`; the call waits for it twice (the three
+ * totals size the outputs; the result is complete on return) and never for the
+ * device. n == 0 gives a valid empty result and touches no device.
+ * CB_EINVAL before any device work, *out NULL: out or w NULL; cb_select's
+ * refusals of the columns; nk > 16; an op outside 0..2; set NULL with nc > 0,
+ * a set[c] above 1, an INSERT that keeps a column, a DELETE with columns; old
+ * arrays with INSERT or DELETE, or not all three of them; cells or cell_off
+ * NULL with rows of at least one cell; host offsets that decrease. After the
+ * size pass: a row's log record of 4 GiB or more (cb_log_replay's limit). */
+#define CB_WRITE_INSERT 0
+#define CB_WRITE_UPDATE 1
+#define CB_WRITE_DELETE 2
+#define CB_WRITTEN_HOST 1
+#define CB_WRITTEN_BADOLD 2
+#define CB_WRITTEN_KEYCTL 4
+typedef struct cb_write {        /* host memory */
+    const uint8_t* ns;           /* the namespace's bytes (NULL with ns_len == 0) */
+    uint64_t ns_len;
+    uint32_t nk;                 /* key columns, <= 16 */
+    const uint8_t* cols;         /* the payload column names, concatenated */
+    const uint64_t* col_off;     /* nc + 1 offsets into cols */
+    const uint8_t* set;          /* nc flags */
+    uint32_t nc;                 /* payload columns, <= 16 */
+    int op;                      /* CB_WRITE_* */
+} cb_write;
+int cb_rows_write(const void* w /* cb_write */, const uint8_t* cells, const uint64_t* cell_off /* n * width + 1 */,
+                  const uint64_t* ts /* n, nullable */, uint64_t ts_all, const int32_t* old_which /* n, nullable */,
+                  const uint8_t* old_vals, const uint64_t* old_val_off /* n + 1 */, uint64_t n, int device,
+                  void* stream, void** out /* cb_written */);
+/* The rows, the bytes of the keys, values and log records, and the rows with
+ * any flag. Every output is nullable. */
+int cb_written_info(const void* written, uint64_t* count, uint64_t* key_bytes, uint64_t* val_bytes,
+                    uint64_t* log_bytes, uint64_t* flagged);
+/* The result's device arrays (NULL all for a batch of no rows): ragged keys
+ * and values with count + 1 offsets each, the log (record i at log_off[i]),
+ * and the flags. They stay valid until cb_written_destroy and are what
+ * cb_sstable_create, cb_filter_insert_var, cb_ring_route_var (keys, key_off,
+ * vals, val_off) and cb_log_replay (log, log_bytes) take; a table made from
+ * them must be finalised (cb_table_wait) before the batch is destroyed. */
+int cb_written_arrays(const void* written, const uint8_t** keys, const uint64_t** key_off, const uint8_t** vals,
+                      const uint64_t** val_off, const uint8_t** log, const uint64_t** log_off,
+                      const uint8_t** flags);
+/* Any of the arrays into host or device memory (every output nullable). */
+int cb_written_copy(const void* written, uint8_t* keys, uint64_t* key_off, uint8_t* vals, uint64_t* val_off,
+                    uint8_t* log, uint64_t* log_off, uint8_t* flags);
+/* Retires the result's memory through the block pool. */
+int cb_written_destroy(void* written);
+/* One row by the same rule on the host (a memtable-sized write; no device):
+ * cell_off holds the row's width + 1 offsets; has_old != 0: old_value[0 ..
+ * old_len) is the old value (UPDATE only). The three lengths are always set;
+ * with out NULL nothing else happens (sizing); else, when cap holds them, out
+ * receives key | value | record. */
+int cb_row_write(const void* w /* cb_write */, const uint8_t* cells, const uint64_t* cell_off, uint64_t ts,
+                 const uint8_t* old_value, uint64_t old_len, int has_old, uint8_t* out, uint64_t cap,
+                 uint64_t* key_len, uint64_t* val_len, uint64_t* log_len, uint8_t* flags);
+
 /* ---- tuning / introspection (bench + tests) ---- */
 /* Path selection: 0 = auto, 1 = force direct (per-key atomics / gathers),
  * 2 = force tiled (LDS-staged filter tiles). Process-wide. */

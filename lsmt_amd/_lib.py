@@ -29,6 +29,8 @@ PATH_AUTO, PATH_DIRECT, PATH_TILED = 0, 1, 2
 XCHG_DENSE, XCHG_SPARSE = 0, 1
 SELECT_JSON, SELECT_META = 0, 1
 ROW_TEXT, ROW_DEAD, ROW_ABSENT, ROW_BADJSON, ROW_EXTRA = 1, 2, 4, 8, 16
+WRITE_INSERT, WRITE_UPDATE, WRITE_DELETE = 0, 1, 2
+WRITTEN_HOST, WRITTEN_BADOLD, WRITTEN_KEYCTL = 1, 2, 4
 COMM_ID_BYTES = 128
 # cb_host_allgather_fn (include/cassbloom.h): int (*)(void* user, const void* send, void* recv, uint64_t bytes)
 HOST_ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
@@ -198,6 +200,12 @@ def load():
         "cb_rows_info": ([P, pu64, pu64, pu64], i32),
         "cb_rows_text": ([P, u8p, P, P, u8p], i32),
         "cb_rows_destroy": ([P], i32),
+        "cb_rows_write": ([P, u8p, P, P, u64, P, u8p, P, u64, i32, P, pp], i32),
+        "cb_written_info": ([P, pu64, pu64, pu64, pu64, pu64], i32),
+        "cb_written_arrays": ([P, pp, pp, pp, pp, pp, pp, pp], i32),
+        "cb_written_copy": ([P, u8p, P, u8p, P, u8p, P, u8p], i32),
+        "cb_written_destroy": ([P], i32),
+        "cb_row_write": ([P, u8p, P, u64, u8p, u64, i32, u8p, u64, pu64, pu64, pu64, u8p], i32),
         "cb_ring_create": ([u8p, P, u32, u32, u32, pp], i32),
         "cb_ring_create_tokens": ([P, P, u64, u32, u32, pp], i32),
         "cb_ring_info": ([P, ctypes.POINTER(u32), ctypes.POINTER(u32), pu64, ctypes.POINTER(u32)], i32),

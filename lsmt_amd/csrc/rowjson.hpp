@@ -182,6 +182,10 @@ struct B64Bytes {
 
 // ---- the key's parts ----
 
+// What stands between two parts: build_row's and build_single_key's join
+// (src/query.rs:730) writes it (rowwrite.hpp), the functions below split at it.
+constexpr uint8_t kKeyPartSep = '|';
+
 // How many parts the key's rest[0..n) has: one more than its separators (an
 // empty rest is one empty part).
 CB_ROW_HD inline uint64_t key_part_count(const uint8_t* rest, uint64_t n) {

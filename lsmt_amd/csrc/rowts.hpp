@@ -24,6 +24,12 @@ constexpr uint64_t b64_sextet(uint8_t c) {
   return c >= 'a' ? c - 'a' + 26u : c >= 'A' ? c - 'A' + 0u : c >= '0' ? c - '0' + 52u : c == '+' ? 62u : 63u;
 }
 
+// Its inverse: the character of 6 bits v < 64 (what STANDARD.encode writes;
+// rowwrite.hpp's log records. The flush keeps its own in flush.hip.)
+constexpr uint8_t b64_char(uint32_t v) {
+  return (uint8_t)(v < 26 ? 'A' + v : v < 52 ? 'a' + (v - 26) : v < 62 ? '0' + (v - 52) : v == 62 ? '+' : '/');
+}
+
 // split_ts(value).0 of decoded bytes p[0..len).
 constexpr uint64_t decoded_ts(const uint8_t* p, uint64_t len) {
   if (len < 8) return 0;

@@ -24,20 +24,6 @@
 namespace cb {
 namespace {
 
-// select_size's slots of one row in the column-major arrays.
-struct ColumnSlots {
-  uint64_t *at, *len;  // (already at the row)
-  uint64_t n;
-  __device__ void set(uint32_t c, uint64_t a, uint64_t l) {
-    at[c * n] = a;
-    len[c * n] = l;
-  }
-  __device__ void get(uint32_t c, uint64_t* a, uint64_t* l) const {
-    *a = at[c * n];
-    *l = len[c * n];
-  }
-};
-
 __device__ __forceinline__ uint32_t row_skip(const SelectRows& r, uint64_t i) {
   if (!r.skip) return r.skip_all;
   return r.skip[last_le(r.nr, i, [&](uint32_t g) { return r.range_off[g]; })];  // the row's range (range_off[0] = 0)

@@ -18,6 +18,21 @@ namespace cb {
 
 constexpr uint32_t kSelectBlock = 256;  // rows per block of both kernels
 
+// A row's slots (rowselect.hpp) in column-major arrays: the device's form, for
+// the selection's kernels and the write's (write.hip).
+struct ColumnSlots {
+  uint64_t *at, *len;  // (already at the row)
+  uint64_t n;
+  __device__ void set(uint32_t c, uint64_t a, uint64_t l) {
+    at[c * n] = a;
+    len[c * n] = l;
+  }
+  __device__ void get(uint32_t c, uint64_t* a, uint64_t* l) const {
+    *a = at[c * n];
+    *l = len[c * n];
+  }
+};
+
 // The rows: row i's key is keys[key_off[i] .. key_off[i + 1]), its value
 // vals[val_off[i] .. val_off[i + 1]); which (nullable: every row is there)
 // says with which[i] < 0 that there is no row i. A row's key parts begin
